@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- SD1.5 + Paint-with-Words images/sec on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: every rank generates `batch` images through the PUBLIC batched
 entry point (paint_with_words_batch / paint_with_words_inpaint_batch: mask build + conditioning + the denoise loop
@@ -20,7 +20,10 @@ All UNets are the random-init stand-ins of the real topologies (seed 1234), buil
 `--gpus N` with N > 1 and no launcher in the environment re-executes itself under torch.distributed.run (one rank per
 GPU, 127.0.0.1 rendezvous); under the driver's own torchrun it uses the ranks it is given.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, warms up, times the K steps, writes the final latents of the last timed step with `--dump-outputs DIR`
+(DIR/latents.npy, float32, every rank's images in global order; the inputs depend on the arguments only) and prints ONE JSON line
+(rank 0) with the driver's contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`: milliseconds of one
+timed step) and `config`. Everything else is measured or checked only with `--full`, which adds to the line
   "roofline"     dominant kernel (self-attention at the finest resolution) TFLOP/s vs the dense MFMA peak, timed live in
                  an instrumented (eager) pass of the same workload: every launch stamps its own start / end device
                  timestamps into a HIP event pair on the launch stream (pww_profile_arm -> hipExtLaunchKernelGGL), i.e.
@@ -594,6 +597,22 @@ def cpu_baseline(args, cfg, request):
     return out
 
 
+# ---- outputs --------------------------------------------------------------------------------------------------------
+
+def dump_outputs(out_dir, lat, request, rank, world, device):
+    """--dump-outputs: the final latents of the last timed step -- what the batched entry point hands its caller -- of every rank's images
+    in global order, as DIR/latents.npy (float32; 64 KB per image). A rank without images contributes none."""
+    if lat is None:
+        h, w = request["rgb"].shape[:2]
+        lat = torch.zeros((0, 4, h // 8, w // 8), device=device)
+    from pww_hip import dist as pdist
+    parts = pdist.gather_latents(lat.float()) if world > 1 else [lat.float()]
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "latents.npy"), torch.cat([p.cpu() for p in parts]).numpy().astype(np.float32))
+        log("outputs written to", out_dir)
+
+
 # ---- launcher -------------------------------------------------------------------------------------------------------
 
 def _free_port():
@@ -645,6 +664,11 @@ def main():
     ap.add_argument("--parity-bar", type=float, default=None, help="rel-L2 bar of the final-latent parity check (default: BASELINE.md section 4's 5e-2 for bf16, "
                     "1e-2 for fp16); the run fails above it")
     ap.add_argument("--dump-latents", default=None, metavar="PREFIX", help="save this rank's final latents of the last timed step to PREFIX_rank<r>.npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path returned in its last step "
+                    "(the final latents of every rank's images, global order) to DIR/latents.npy as float32")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: the final-latent parity check against the committed fixture, "
+                    "the instrumented roofline / per-kernel pass with its live counters, the reference's ops on this GPU and the CPU baseline "
+                    "(each still subject to its own --no-* / --cpu-steps switch)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: spawn / rendezvous (gloo) / broadcast a 1/8-width model and the request, print the line with value null")
     args = ap.parse_args()
 
@@ -664,6 +688,12 @@ def main():
             cfg[k_cfg] = getattr(args, k_arg)
     if args.steps is None:
         args.steps = 4 if args.config == 2 else 1
+    if args.config == 2:
+        # MIOpen's find search also times its naive reference convolution (ConvDirectNaiveConvFwd), 100 - 1000x slower than the implicit-GEMM
+        # solvers that win every one of the headline's 21 convolution shapes: 17.5 of the 26 s of its first warm-up step under a cold MIOpen
+        # cache (MIOpen's own log). Left out of the search, the implicit-GEMM solvers compete as before and that step takes 6.5 - 7 s.
+        # (Set before the first MIOpen call.)
+        os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD", "0")
 
     from pww_hip import dist as pdist, ops
     import pww_hip
@@ -771,12 +801,13 @@ def main():
     # instead of repeating the search N times side by side. One node: the ranks share a file system.
     staged = world > 1 and args.warmup > 0 and on_gpu and os.environ.get("PWW_MIOPEN_FIND", "1") != "0"
     db_files = 0
-    if on_gpu and os.environ.get("PWW_FIND_PREWARM", "1") == "1" and os.environ.get("PWW_MIOPEN_FIND", "1") != "0" and args.warmup > 0 and not args.tiny:
+    prewarm = os.environ.get("PWW_FIND_PREWARM", "0" if args.config == 2 else "1") == "1"
+    if on_gpu and prewarm and os.environ.get("PWW_MIOPEN_FIND", "1") != "0" and args.warmup > 0 and not args.tiny:
         # One eager pass in MIOpen's immediate mode BEFORE the warm-up pass that carries the find search: clocks, allocator and code caches are
         # warm when the solvers are timed. The search times every candidate once, and with a cold GPU its choices moved the batched configs from
         # process to process on ONE box (config 4: 10.5 / 8.7 / 10.4 / 9.1 / 8.7 images/s; with the pre-pass 10.0 / 10.0 / 9.6 / 9.8; config 5:
-        # 2.88 / 2.31 / 2.99 against 2.79 / 3.08 / 2.88; configs 2 and 3: no difference -- profiles/r06_miopen_find_prepass.txt). Untimed, 0.3 - 1.4 s;
-        # PWW_FIND_PREWARM=0 skips it.
+        # 2.88 / 2.31 / 2.99 against 2.79 / 3.08 / 2.88; configs 2 and 3: no difference -- profiles/r06_miopen_find_prepass.txt). Untimed, but
+        # 19 - 26 s under a cold MIOpen cache: the headline workload (config 2) skips it by default; PWW_FIND_PREWARM=1 / 0 forces it on / off.
         prev_bm, prev_mode = torch.backends.cudnn.benchmark, pw_api.DEFAULT_MODE
         torch.backends.cudnn.benchmark, pw_api.DEFAULT_MODE = False, "eager"
         try:
@@ -841,17 +872,19 @@ def main():
         smp.check_errors()            # fused hand-off time-outs of any timed request (raises; the requests are complete: synchronised above)
     verdict = None if lat is None or bool(torch.isfinite(lat).all()) else "non-finite latents on rank %d" % rank
     # final-latent parity of THIS run's configuration against the committed fixture of the workload (rank 0 holds global images 0..: the fixture's)
-    par = parity_check(args, cfg, lat0, my_lo) if rank == 0 else None
+    par = parity_check(args, cfg, lat0, my_lo) if rank == 0 and args.full else None
     if par is not None:
         result["parity"] = par
         log("parity of the timed configuration: rel-L2 %.3e (bar %.0e) vs %s" % (par["rel_l2"], par["bar"], par["fixture"]))
         if not par["ok"] and verdict is None:
             verdict = "final latents of global step 0 are %.3e (rel-L2) away from %s: above the %.0e bar" % (par["rel_l2"], par["fixture"], par["bar"])
-    elif rank == 0:
+    elif rank == 0 and args.full:
         result["parity"] = None       # (not the fixture's workload: overridden dtype / scheduler / steps / guidance, or --tiny)
     fail_together(verdict)
     if args.dump_latents and lat is not None:
         np.save("%s_rank%d.npy" % (args.dump_latents, rank), lat.float().cpu().numpy())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lat, request, rank, world, device)
     if args.tiny:
         result["data"] = "synthetic (1/8-width model: plumbing test, not a measurement)"
     log("timed region done: %.3f s for %d steps" % (elapsed, args.steps))
@@ -864,7 +897,7 @@ def main():
     result["config"]["per_rank"] = {"seconds": [round(t, 4) for t in per_rank_s],
                                     "images_per_s": [round(args.steps * (hi - lo) / t, 4) for (lo, hi), t in zip(lo_hi, per_rank_s)]}
 
-    if rank == 0 and not args.no_roofline_pass:
+    if rank == 0 and args.full and not args.no_roofline_pass:
         # instrumented pass (same workload, folded mode so single launches can be bracketed by HIP events
         # on the launch stream): dominant kernel = self-attention at the finest resolution
         timer = EventTimer()
@@ -977,10 +1010,10 @@ def main():
             log("live counters done in %.1f s" % (time.perf_counter() - t_pmc), lv, cross, cross16)
         from pww_hip import _lib as _pww_lib
         _pww_lib.load().pww_profile_reset()
-    if rank == 0 and world == 1 and not args.no_reference_ops and cfg["kind"] == "txt2img":
+    if rank == 0 and world == 1 and args.full and not args.no_reference_ops and cfg["kind"] == "txt2img":
         result["reference_ops_same_gpu"] = reference_ops_same_gpu(cfg, tools, request, device, dtype, args.guidance)
         log("reference-ops pass done", result["reference_ops_same_gpu"])
-    if rank == 0 and world == 1 and args.cpu_steps > 0 and cfg["kind"] == "txt2img":
+    if rank == 0 and world == 1 and args.full and args.cpu_steps > 0 and cfg["kind"] == "txt2img":
         result["cpu_baseline"] = cpu_baseline(args, cfg, request)
     if rank == 0:
         print(json.dumps(result), file=json_out, flush=True)

@@ -38,7 +38,7 @@ def test_bench_parity_in_the_timed_configuration(gpu_device, config):
     other loop tests run immediate mode and NCHW) -- one warm-up step (global step 0 = the fixture's seeds) and one timed step: the line's
     `parity` holds the rel-L2 of the warm-up step's final latents against the reference-loop fixture, inside BASELINE.md's bar AND inside
     the calibrated bar of the NCHW loop tests (1.5 x the unfused torch path's drift + 2e-3)."""
-    line = _run_bench(["--config", str(config), "--steps", "1", "--warmup", "1", "--no-roofline-pass", "--no-reference-ops", "--cpu-steps", "0"],
+    line = _run_bench(["--full", "--config", str(config), "--steps", "1", "--warmup", "1", "--no-roofline-pass", "--no-reference-ops", "--cpu-steps", "0"],
                       env_extra={"PWW_MIOPEN_FIND": "1"})
     par = line["parity"]
     print("bench.py --config %d parity: %s" % (config, par))
@@ -52,7 +52,7 @@ def test_bench_parity_in_the_timed_configuration(gpu_device, config):
 def test_bench_fails_above_the_parity_bar(gpu_device):
     """The run FAILS -- non-zero exit, no json line -- when the final latents leave the bar (here: a bar no half-precision run can meet)."""
     env = dict(os.environ, PWW_BENCH_VERBOSE="0", PWW_MIOPEN_FIND="0")
-    out = subprocess.run([sys.executable, os.path.join(cases.REPO, "bench.py"), "--steps", "1", "--warmup", "1", "--no-roofline-pass", "--no-reference-ops",
+    out = subprocess.run([sys.executable, os.path.join(cases.REPO, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--no-roofline-pass", "--no-reference-ops",
                           "--cpu-steps", "0", "--parity-bar", "1e-6"], capture_output=True, text=True, timeout=900, env=env, cwd=cases.REPO)
     assert out.returncode != 0 and out.stdout.strip() == ""
     assert "above the 1e-06 bar" in out.stderr
@@ -61,7 +61,7 @@ def test_bench_fails_above_the_parity_bar(gpu_device):
 def test_two_ranks_stage_their_warmup(gpu_device, tmp_path):
     """bench.py --gpus 2 (two ranks sharing this GPU over gloo, 1/8-width model, MIOpen find mode on): rank 0 warms up first, rank 1 adopts
     its MIOpen user db before its own first convolution; the line carries every rank's warm-up seconds and the files adopted."""
-    line = _run_bench(["--gpus", "2", "--config", "3", "--batch", "1", "--denoise-steps", "2", "--steps", "1", "--warmup", "1", "--no-roofline-pass",
+    line = _run_bench(["--full", "--gpus", "2", "--config", "3", "--batch", "1", "--denoise-steps", "2", "--steps", "1", "--warmup", "1", "--no-roofline-pass",
                        "--no-reference-ops", "--cpu-steps", "0", "--tiny"],
                       env_extra={"PWW_DIST_ONE_DEVICE": "1", "PWW_MIOPEN_FIND": "1", "PWW_MIOPEN_DB_BASE": str(tmp_path / "miopen")})
     db = line["config"]["miopen_db"]

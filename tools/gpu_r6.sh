@@ -2,7 +2,7 @@
 # Round-6 GPU runner: `bash tools/gpu_r6.sh <stage> [...]`; everything lands under gpurun_out/r6_<stage>*.
 export TMPDIR=/tmp
 mkdir -p gpurun_out; O=gpurun_out
-SHORT="--steps 3 --warmup 1 --cpu-steps 0 --no-reference-ops --no-live-counters"
+SHORT="--full --steps 3 --warmup 1 --cpu-steps 0 --no-reference-ops --no-live-counters"
 summ() { python - "$1" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -26,7 +26,7 @@ bench)
   timeout 400 python bench.py $SHORT > $O/r6_bench.json 2> $O/r6_bench.log; tail -2 $O/r6_bench.log; summ $O/r6_bench.json
   ;;
 benchfull)
-  timeout 900 python bench.py > $O/r6_bench_default.json 2> $O/r6_bench_default.log; tail -2 $O/r6_bench_default.log; summ $O/r6_bench_default.json
+  timeout 900 python bench.py --full > $O/r6_bench_default.json 2> $O/r6_bench_default.log; tail -2 $O/r6_bench_default.log; summ $O/r6_bench_default.json
   ;;
 native)
   (cd tests/native && timeout 900 ./attn_check --quick > ../../$O/r6_native.log 2>&1; grep -c "^PASS" ../../$O/r6_native.log; grep -v "^PASS\|^TIME\|^TIMELINE" ../../$O/r6_native.log | tail -15)
@@ -39,7 +39,7 @@ subset)
   ;;
 configs)
   for c in 3 4 5; do
-    timeout 900 python bench.py --config $c --steps 1 --warmup 1 --cpu-steps 0 --no-reference-ops --no-live-counters > $O/r6_bench_c$c.json 2> $O/r6_bench_c$c.log; summ $O/r6_bench_c$c.json
+    timeout 900 python bench.py --full --config $c --steps 1 --warmup 1 --cpu-steps 0 --no-reference-ops --no-live-counters > $O/r6_bench_c$c.json 2> $O/r6_bench_c$c.log; summ $O/r6_bench_c$c.json
   done
   ;;
 k1route)
@@ -62,15 +62,15 @@ preload)
   rm -f $O/r6_preload_ab.txt
   for i in 1 2 3; do for v in preload nopreload; do
     L=""; [ $v = nopreload ] && L="$PWD/paint-with-words-sd_amd/build/ab/libpww_hip_nopreload.so"
-    PWW_HIP_LIB=${L:-$PWD/paint-with-words-sd_amd/pww_hip/libpww_hip.so} timeout 300 python bench.py --steps 6 --warmup 1 --no-roofline-pass --no-reference-ops --cpu-steps 0 2> /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['ms_per_step'], d['parity']['rel_l2'])" | tee -a $O/r6_preload_ab.txt
+    PWW_HIP_LIB=${L:-$PWD/paint-with-words-sd_amd/pww_hip/libpww_hip.so} timeout 300 python bench.py --full --steps 6 --warmup 1 --no-roofline-pass --no-reference-ops --cpu-steps 0 2> /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['ms_per_step'], d['parity']['rel_l2'])" | tee -a $O/r6_preload_ab.txt
   done; done
   ;;
 prof)
   OUT=/tmp/pww_prof_r06; rm -rf $OUT; R=$PWD
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $OUT -o run -- python $R/bench.py --steps 2 --warmup 1 --cpu-steps 0 --no-reference-ops --no-live-counters > $R/$O/r6_bench_c2_prof.json 2> $R/$O/r6_bench_c2_prof.log) || true
+  (cd "$TMPDIR" && timeout 900 rocprofv3 --kernel-trace --stats -d $OUT -o run -- python $R/bench.py --full --steps 2 --warmup 1 --cpu-steps 0 --no-reference-ops --no-live-counters > $R/$O/r6_bench_c2_prof.json 2> $R/$O/r6_bench_c2_prof.log) || true
   DB=$(find $OUT -name "*.db" | head -1)
   W=$(grep "timed region CLOCK_MONOTONIC" $O/r6_bench_c2_prof.log | sed 's/.*ns //')
-  { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --cpu-steps 0 --no-reference-ops --no-live-counters (round 6)"; echo; echo "## pww kernels, whole process (workload + roofline pass)";
+  { echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 2 --warmup 1 --cpu-steps 0 --no-reference-ops --no-live-counters (round 6)"; echo; echo "## pww kernels, whole process (workload + roofline pass)";
     python tools/rocpd_stats.py "$DB" --top 60 --grid --match pww --split-b2b attn_fwd_fold_kernel; echo; echo "## pww kernels of the TIMED steps (hipGraph replay: what the product pays per launch)"; python tools/rocpd_stats.py "$DB" --top 60 --grid --match pww --window $W; echo; echo "## every kernel of the TIMED steps"; python tools/rocpd_stats.py "$DB" --top 45 --grid --window $W; } > $O/r6_bench_c2_kernel_stats.md 2>&1
   tail -1 $O/r6_bench_c2_prof.json | cut -c1-200; grep -c "" $O/r6_bench_c2_kernel_stats.md
   ;;
@@ -88,7 +88,7 @@ igemm)
   # zero + cast: 1736 + 1736 launches per 2 images in the trace); with the solver disabled find mode picks among the others
   rm -f $O/r6_igemm_ab.txt
   for i in 1 2; do for v in 1 0; do
-    MIOPEN_DEBUG_CONV_IMPLICIT_GEMM_ASM_FWD_GTC_XDLOPS_NHWC=$v timeout 400 python bench.py --steps 6 --warmup 1 --no-roofline-pass --no-reference-ops --cpu-steps 0 2> /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ASM_FWD_GTC_XDLOPS_NHWC=$v', d['value'], d['ms_per_step'], d['parity']['rel_l2'], d['config']['warmup_s'])" | tee -a $O/r6_igemm_ab.txt
+    MIOPEN_DEBUG_CONV_IMPLICIT_GEMM_ASM_FWD_GTC_XDLOPS_NHWC=$v timeout 400 python bench.py --full --steps 6 --warmup 1 --no-roofline-pass --no-reference-ops --cpu-steps 0 2> /dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ASM_FWD_GTC_XDLOPS_NHWC=$v', d['value'], d['ms_per_step'], d['parity']['rel_l2'], d['config']['warmup_s'])" | tee -a $O/r6_igemm_ab.txt
   done; done
   ;;
 hot)
