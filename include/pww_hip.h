@@ -308,6 +308,32 @@ int pww_geglu(const void *h, void *y, int64_t rows, int32_t D, int64_t h_stride,
 int pww_bias_residual(const void *r, const void *v, const void *bias, void *y, int32_t B, int32_t C, int32_t HW, int32_t layout, int32_t dtype, void *stream);
 
 /*
+ * 3 x 3 convolution, padding 1, groups 1, as an implicit GEMM over NHWC tensors (the UNet's ResnetBlock2D / Downsample2D / Upsample2D convs
+ * on channels_last tensors). No ABI version bump: pww_conv_desc_t carries its own size.
+ *   x         [B][Hin][Win][Cin]        (NHWC, contiguous)
+ *   w         [Cout][3][3][Cin]         (the storage order of a channels_last nn.Conv2d weight)
+ *   bias      [Cout] or NULL;  residual [B][Ho][Wo][Cout] or NULL (may alias y);  y [B][Ho][Wo][Cout]
+ *   upsample  1: the input is first upsampled 2x nearest (Upsample2D), fused into the gather; stride 1 only
+ *   Ho = (Hin * (1 + upsample) - 1) / stride + 1, likewise Wo.
+ * y = T(residual + T(T(conv) + bias)) with the roundings of conv -> pww_bias_residual (each term only when given); fp32 accumulation.
+ * Requirements: Cin, Cout multiples of 64, stride 1 or 2; PWW_ENOTSUP otherwise. tile_n / splitk: 0 = the library's choice (64 / 128 output
+ * channels per tile; K split so that the launch about fills the device). With a K split the fp32 partials go to `workspace` (at least
+ * pww_conv3x3_workspace_bytes(desc) bytes, 16-byte aligned, contents need not be initialised) and a second launch folds them in fixed
+ * order: no atomics, results bitwise repeatable.
+ */
+typedef struct pww_conv_desc {
+    uint32_t size;        /* sizeof(pww_conv_desc_t) */
+    int32_t dtype;        /* PWW_DTYPE_* */
+    int32_t B, Hin, Win, Cin, Cout;
+    int32_t stride, upsample;
+    int32_t tile_n, splitk;
+    int32_t _pad;
+} pww_conv_desc_t;
+size_t pww_conv3x3_workspace_bytes(const pww_conv_desc_t *desc);
+int pww_conv3x3_fwd(const void *x, const void *w, const void *bias, const void *residual, void *y, const pww_conv_desc_t *desc, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
+/*
  * Per-image global statistics of the raw score tensor S = Q K^T over all heads, rows and keys
  * (what weight_function reduces: qk.max(), qk.min(), qk.mean(), qk.std()).
  *   stats      double [B][4] = { max, min, sum, sum of squares } per image b (fully overwritten).

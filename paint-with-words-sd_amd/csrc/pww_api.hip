@@ -199,6 +199,9 @@ int group_norm_fwd(const void *x, const void *pre_c, const void *add_bc, const v
 int add_layer_norm(const void *a, const void *x, const void *gamma, const void *beta, void *s, void *y, const pww_ln_desc_t *d, hipStream_t stream, const void *post_bias = nullptr);
 int geglu(const void *h, void *y, int64_t rows, int32_t D, int64_t h_stride, int64_t y_stride, int32_t dtype, hipStream_t stream);
 int bias_residual(const void *r, const void *v, const void *bias, void *y, int32_t B, int32_t C, int32_t HW, int32_t layout, int32_t dtype, hipStream_t stream);
+size_t conv3x3_workspace_bytes(const pww_conv_desc_t *d);
+int conv3x3_fwd(const void *x, const void *w, const void *bias, const void *residual, void *y, const pww_conv_desc_t *d, void *workspace,
+                size_t workspace_bytes, hipStream_t stream);
 
 }  // namespace pww
 
@@ -384,6 +387,11 @@ int pww_geglu(const void *h, void *y, int64_t rows, int32_t D, int64_t h_stride,
 }
 int pww_bias_residual(const void *r, const void *v, const void *bias, void *y, int32_t B, int32_t C, int32_t HW, int32_t layout, int32_t dtype, void *stream) {
     return pww::bias_residual(r, v, bias, y, B, C, HW, layout, dtype, static_cast<hipStream_t>(stream));
+}
+size_t pww_conv3x3_workspace_bytes(const pww_conv_desc_t *desc) { return pww::conv3x3_workspace_bytes(desc); }
+int pww_conv3x3_fwd(const void *x, const void *w, const void *bias, const void *residual, void *y, const pww_conv_desc_t *desc, void *workspace,
+                    size_t workspace_bytes, void *stream) {
+    return pww::conv3x3_fwd(x, w, bias, residual, y, desc, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

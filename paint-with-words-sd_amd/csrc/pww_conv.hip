@@ -1,0 +1,295 @@
+// 3 x 3 convolution (padding 1) over NHWC tensors as an implicit GEMM on gfx950 MFMA (pww_conv3x3_fwd):
+//
+//   y[m, n] = sum_k X[m, k] * W[n, k],   m = (b, oy, ox),  n = output channel,  k = (ky, kx, ci)
+//
+// K is ordered (ky, kx, ci), the layout of a channels_last nn.Conv2d weight ([Cout][3][3][Cin]), so one K-slab of 64 is a contiguous run of
+// 64 channels of ONE tap: 16-byte loads straight from the activation for X and from the weight row for W. The padding halo (and the
+// M tail) loads from a clamped address and selects zero after the load -- no branch around a load. Stride 2 (Downsample2D) and a
+// nearest 2x upsample of the input (Upsample2D: the gather reads x[iy >> 1][ix >> 1]) are index arithmetic of the same gather.
+//
+// Tile: 128 (M) x BN (N, 64 or 128) x 64 (K) per 256-thread workgroup, 2 x 2 waves, mfma_f32_16x16x32 with the WEIGHT as the A operand:
+// the accumulator then holds 4 consecutive channels of one pixel per lane (8-byte stores, 8-byte bias / residual loads). Register-staged
+// double buffer, one barrier per K-slab; LDS rows of 128 bytes with the 16-byte chunk index XOR-ed by (row & 7).
+//
+// Split-K (the 16 x 16 and 8 x 8 levels have too few tiles for 256 CUs): each workgroup writes its fp32 partial tile to a caller-owned
+// workspace, a second launch folds the partials in fixed order and applies the epilogue. No atomics, no inter-workgroup waits: results
+// are bitwise repeatable.
+//
+// Epilogue, with the stock sequence's rounding points (T = storage type):  v = T(acc);  v = T(v + bias[n]) (bias);  v = T(residual + v)
+// (residual) -- exactly what conv -> pww_bias_residual computed.
+#include "pww_common.h"
+
+namespace pww {
+
+namespace {
+
+constexpr int CV_BM = 128, CV_THREADS = 256;
+
+__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+// cold kernel arguments (behind the preloaded hot ones)
+struct ConvCold {
+    const void *bias, *residual;
+    int nsplit, nslab;
+};
+
+// bijective block-id remap: consecutive logical ids (tiles that share weight columns) on one XCD (guide T1)
+__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
+    const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+}
+
+template <typename T>
+__device__ __forceinline__ void epilogue4(const f32x4 &a, const ConvCold &cold, T *y, long off, int n) {
+    typedef typename Vec<T>::v4 V4;
+    V4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (T)a[j];
+    if (cold.bias) {
+        const V4 b = *reinterpret_cast<const V4 *>(reinterpret_cast<const T *>(cold.bias) + n);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (T)((float)o[j] + (float)b[j]);
+    }
+    if (cold.residual) {
+        const V4 r = *reinterpret_cast<const V4 *>(reinterpret_cast<const T *>(cold.residual) + off);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (T)((float)r[j] + (float)o[j]);
+    }
+    *reinterpret_cast<V4 *>(y + off) = o;
+}
+
+// geo = stride | (upsample << 4). Hot arguments first: 14 dwords preloaded into SGPRs.
+template <typename T, int BN, bool SPLIT>
+__global__ void __launch_bounds__(CV_THREADS) conv3x3_kernel(const T *__restrict__ x, const T *__restrict__ w, void *__restrict__ out, int M, int N,
+                                                            int Cin, int Hin, int Win, int Wo, int HWo, const ConvCold cold) {
+    typedef typename Vec<T>::v8 V8;
+    constexpr int BM = CV_BM, XL = BM * 8 / CV_THREADS, WL = BN * 8 / CV_THREADS, RM = 4, RN = BN / 32;
+    constexpr int XBYTES = BM * 128, STAGE = (BM + BN) * 128;
+    __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
+
+    const int geo = cold.nslab >> 24;                       // (packed by the host: stride | upsample << 4)
+    const int nslab = cold.nslab & 0xffffff;
+    const int stride = geo & 15, up = geo >> 4;
+    const int Hv = Hin << up, Wv = Win << up;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int ntm = (M + BM - 1) / BM;
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile = SPLIT ? bid / cold.nsplit : bid, ks = SPLIT ? bid % cold.nsplit : 0;
+    const int tm = tile % ntm, tn = tile / ntm;
+    const int s_begin = SPLIT ? (int)((long)ks * nslab / cold.nsplit) : 0;
+    const int s_end = SPLIT ? (int)((long)(ks + 1) * nslab / cold.nsplit) : nslab;
+    const int K9 = 9 * Cin;
+
+    // the gather geometry of this thread's XL rows (row (tid >> 3) + 32 i, 16-byte chunk tid & 7 of the slab)
+    const int c = tid & 7;
+    int pix[XL], y0[XL], x0[XL];
+#pragma unroll
+    for (int i = 0; i < XL; ++i) {
+        int m = tm * BM + (tid >> 3) + 32 * i;
+        m = m < M ? m : M - 1;
+        const int b = m / HWo, rem = m - b * HWo, oy = rem / Wo, ox = rem - oy * Wo;
+        pix[i] = b * Hin * Win;
+        y0[i] = oy * stride - 1;
+        x0[i] = ox * stride - 1;
+    }
+    const T *wrow = w + (long)(tn * BN + (tid >> 3)) * K9 + c * 8;
+    const int swz = ((c ^ ((tid >> 3) & 7)) << 4);          // LDS byte offset of this thread's chunk within its row
+
+    u32x4 xr[XL], wr[WL];
+    unsigned xok = 0;
+    int tap = s_begin / (Cin >> 6), ci0 = (s_begin - tap * (Cin >> 6)) << 6;
+    auto load = [&](int s) {
+        const int ky = tap / 3, kx = tap - ky * 3;
+#pragma unroll
+        for (int i = 0; i < XL; ++i) {
+            const int iyv = y0[i] + ky, ixv = x0[i] + kx;
+            const bool ok = (unsigned)iyv < (unsigned)Hv && (unsigned)ixv < (unsigned)Wv;
+            const int iy = ok ? iyv >> up : 0, ix = ok ? ixv >> up : 0;
+            xr[i] = *reinterpret_cast<const u32x4 *>(x + (unsigned)((pix[i] + iy * Win + ix) * Cin + ci0 + c * 8));
+            xok = (xok & ~(1u << i)) | ((unsigned)ok << i);
+        }
+#pragma unroll
+        for (int j = 0; j < WL; ++j) wr[j] = *reinterpret_cast<const u32x4 *>(wrow + (long)(32 * j) * K9 + s * 64);
+        ci0 += 64;
+        if (ci0 == Cin) { ci0 = 0; ++tap; }
+    };
+    auto store = [&](int buf) {
+        char *base = lds + buf * STAGE;
+#pragma unroll
+        for (int i = 0; i < XL; ++i) {
+            const u32x4 z = {0u, 0u, 0u, 0u};           // (the halo's select sits here, after the compute: the loads stay in flight across it)
+            *reinterpret_cast<u32x4 *>(base + ((tid >> 3) + 32 * i) * 128 + swz) = (xok >> i) & 1u ? xr[i] : z;
+        }
+#pragma unroll
+        for (int j = 0; j < WL; ++j) *reinterpret_cast<u32x4 *>(base + XBYTES + ((tid >> 3) + 32 * j) * 128 + swz) = wr[j];
+    };
+
+    f32x4 acc[RN][RM];
+#pragma unroll
+    for (int r = 0; r < RN; ++r)
+#pragma unroll
+        for (int i = 0; i < RM; ++i) acc[r][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int fr = lane & 15, fq = lane >> 4;
+    if (s_begin < s_end) {
+        load(s_begin);
+        store(0);
+        __syncthreads();
+    }
+    for (int s = s_begin; s < s_end; ++s) {
+        const int cur = (s - s_begin) & 1;
+        if (s + 1 < s_end) load(s + 1);
+        const char *bx = lds + cur * STAGE, *bw = bx + XBYTES;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            V8 xf[RM], wf[RN];
+#pragma unroll
+            for (int i = 0; i < RM; ++i) {
+                const int row = wm * 64 + i * 16 + fr;
+                xf[i] = *reinterpret_cast<const V8 *>(bx + row * 128 + (((kk * 4 + fq) ^ (row & 7)) << 4));
+            }
+#pragma unroll
+            for (int r = 0; r < RN; ++r) {
+                const int row = wn * (BN / 2) + r * 16 + fr;
+                wf[r] = *reinterpret_cast<const V8 *>(bw + row * 128 + (((kk * 4 + fq) ^ (row & 7)) << 4));
+            }
+#pragma unroll
+            for (int r = 0; r < RN; ++r)
+#pragma unroll
+                for (int i = 0; i < RM; ++i) acc[r][i] = mfma16(wf[r], xf[i], acc[r][i]);
+        }
+        if (s + 1 < s_end) store(cur ^ 1);
+        __syncthreads();
+    }
+
+    // lane holds D[n = 16 r + 4 fq + j][m = 16 i + fr] of its wave's sub-tile
+#pragma unroll
+    for (int i = 0; i < RM; ++i) {
+        const int m = tm * BM + wm * 64 + i * 16 + fr;
+        if (m >= M) continue;
+#pragma unroll
+        for (int r = 0; r < RN; ++r) {
+            const int n = tn * BN + wn * (BN / 2) + r * 16 + fq * 4;
+            if (SPLIT) *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(out) + ((long)ks * M + m) * N + n) = acc[r][i];
+            else epilogue4<T>(acc[r][i], cold, reinterpret_cast<T *>(out), (long)m * N + n, n);
+        }
+    }
+}
+
+// fold the split-K partials [nsplit][M][N] in split order, then the epilogue: one thread per 4 channels of one pixel
+template <typename T>
+__global__ void __launch_bounds__(256) conv3x3_fold_kernel(const float *__restrict__ ws, T *__restrict__ y, long n4, int N, long MN, const ConvCold cold) {
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n4) return;
+    const long off = q * 4;
+    f32x4 a = *reinterpret_cast<const f32x4 *>(ws + off);
+    for (int s = 1; s < cold.nsplit; ++s) a += *reinterpret_cast<const f32x4 *>(ws + s * MN + off);
+    epilogue4<T>(a, cold, y, off, (int)(off % N));
+}
+
+// Tile width and K split per GEMM shape (M = B Ho Wo, N = Cout, K-slabs = 9 Cin / 64), measured on MI355X (tools/time_conv3x3.py --sweep,
+// profiles/conv3x3_sweep.md): the SD1.5 UNet's convolutions at 2 and 16 rows. The fastest split keeps ~15 K-slabs per workgroup and
+// 2 - 4 workgroups per CU; shapes not listed take the rule below (about 480 workgroups, at least 8 K-slabs per split).
+struct ConvTune { int M, N, nslab, bn, nsplit; };
+constexpr ConvTune CONV_TUNED[] = {
+    // 2 rows (batch 1 with classifier-free guidance)
+    {8192, 320, 45, 64, 2}, {8192, 320, 90, 64, 4}, {8192, 320, 135, 64, 3}, {8192, 640, 90, 128, 3},
+    {2048, 320, 45, 64, 6}, {2048, 640, 45, 64, 3}, {2048, 640, 90, 128, 6}, {2048, 640, 135, 128, 6}, {2048, 640, 180, 128, 6},
+    {2048, 640, 270, 128, 6}, {2048, 1280, 180, 128, 3},
+    {512, 640, 90, 64, 6}, {512, 1280, 90, 64, 6}, {512, 1280, 180, 128, 12}, {512, 1280, 270, 128, 12}, {512, 1280, 360, 128, 12},
+    {128, 1280, 180, 64, 12}, {128, 1280, 360, 64, 24},
+    // 16 rows (batch 8)
+    {65536, 640, 90, 128, 1}, {16384, 1280, 180, 128, 1},
+    {4096, 640, 90, 128, 3}, {4096, 1280, 90, 128, 3}, {4096, 1280, 180, 128, 3}, {4096, 1280, 270, 128, 3}, {4096, 1280, 360, 128, 3},
+    {1024, 1280, 180, 128, 6}, {1024, 1280, 360, 128, 6},
+};
+
+struct ConvPlan {
+    int M, Ho, Wo, bn, nsplit, nslab, ntiles;
+};
+
+bool plan_conv(const pww_conv_desc_t *d, ConvPlan *p) {
+    if (!d || d->size < sizeof(pww_conv_desc_t)) { set_error("conv3x3: descriptor missing or older than this library (size %u)", d ? d->size : 0u); return false; }
+    const int up = d->upsample, s = d->stride;
+    if ((d->dtype != PWW_DTYPE_F16 && d->dtype != PWW_DTYPE_BF16) || d->B < 1 || d->Hin < 1 || d->Win < 1 || d->Cin < 64 || d->Cin % 64 != 0
+        || d->Cout < 64 || d->Cout % 64 != 0 || (s != 1 && s != 2) || (up != 0 && up != 1) || (up && s != 1) || d->Cin > 65536 || d->Cout > 65536) {
+        set_error("conv3x3: unsupported (dtype %d B %d %dx%d Cin %d Cout %d stride %d upsample %d): Cin and Cout multiples of 64, stride 1 or 2, "
+                  "upsample only at stride 1", d->dtype, d->B, d->Hin, d->Win, d->Cin, d->Cout, s, up);
+        return false;
+    }
+    const int Hv = d->Hin << up, Wv = d->Win << up;
+    p->Ho = (Hv - 1) / s + 1;
+    p->Wo = (Wv - 1) / s + 1;
+    const long M = (long)d->B * p->Ho * p->Wo;
+    if ((long)d->B * d->Hin * d->Win * d->Cin >= (1L << 31) || M * d->Cout >= (1L << 31)) { set_error("conv3x3: tensor of 2^31 elements or more"); return false; }
+    p->M = (int)M;
+    p->nslab = 9 * d->Cin / 64;
+    const ConvTune *tuned = nullptr;
+    for (const ConvTune &t : CONV_TUNED)
+        if (t.M == p->M && t.N == d->Cout && t.nslab == p->nslab) tuned = &t;
+    p->bn = d->tile_n ? d->tile_n : tuned ? tuned->bn : (d->Cout % 128 == 0 ? 128 : 64);
+    if ((p->bn != 64 && p->bn != 128) || d->Cout % p->bn != 0) { set_error("conv3x3: tile_n %d does not divide Cout %d", d->tile_n, d->Cout); return false; }
+    p->ntiles = (p->M + CV_BM - 1) / CV_BM * (d->Cout / p->bn);
+    int ns = d->splitk;
+    if (ns <= 0 && tuned && p->bn == tuned->bn) ns = tuned->nsplit;
+    if (ns <= 0) {          // about 480 workgroups (2 per CU), at least 8 K-slabs per split
+        ns = (480 + p->ntiles / 2) / p->ntiles;
+        if (ns > p->nslab / 8) ns = p->nslab / 8;
+        if (ns < 1) ns = 1;
+    }
+    if (ns > p->nslab || ns > 64) { set_error("conv3x3: split %d exceeds the %d K-slabs (or 64)", ns, p->nslab); return false; }
+    p->nsplit = ns;
+    return true;
+}
+
+template <typename T>
+int conv_launch(const ConvPlan &p, const pww_conv_desc_t *d, const void *x, const void *w, const void *bias, const void *residual, void *y, void *ws,
+                hipStream_t stream) {
+    ConvCold cold{bias, residual, p.nsplit, p.nslab | ((d->stride | (d->upsample << 4)) << 24)};
+    const T *xt = static_cast<const T *>(x), *wt = static_cast<const T *>(w);
+    const int N = d->Cout, HWo = p.Ho * p.Wo;
+    const dim3 grid(p.ntiles * p.nsplit), block(CV_THREADS);
+    if (p.nsplit == 1) {
+        if (p.bn == 128) launch_timed(conv3x3_kernel<T, 128, false>, grid, block, 0, stream, xt, wt, y, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
+        else launch_timed(conv3x3_kernel<T, 64, false>, grid, block, 0, stream, xt, wt, y, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
+        return check_hip(hipGetLastError(), "conv3x3 launch");
+    }
+    if (p.bn == 128) launch_timed(conv3x3_kernel<T, 128, true>, grid, block, 0, stream, xt, wt, ws, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
+    else launch_timed(conv3x3_kernel<T, 64, true>, grid, block, 0, stream, xt, wt, ws, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
+    const long MN = (long)p.M * N, n4 = MN / 4;
+    launch_timed(conv3x3_fold_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, static_cast<const float *>(ws), static_cast<T *>(y), n4,
+                 N, MN, cold);
+    return check_hip(hipGetLastError(), "conv3x3 fold launch");
+}
+
+bool al16(const void *a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
+
+}  // namespace
+
+size_t conv3x3_workspace_bytes(const pww_conv_desc_t *d) {
+    ConvPlan p;
+    if (!plan_conv(d, &p)) return 0;
+    return p.nsplit > 1 ? (size_t)p.nsplit * p.M * d->Cout * sizeof(float) : 0;
+}
+
+int conv3x3_fwd(const void *x, const void *w, const void *bias, const void *residual, void *y, const pww_conv_desc_t *d, void *workspace,
+                size_t workspace_bytes, hipStream_t stream) {
+    ConvPlan p;
+    if (!plan_conv(d, &p)) return PWW_ENOTSUP;
+    if (!x || !w || !y) { set_error("conv3x3: x, w and y are required"); return PWW_EINVAL; }
+    if (!al16(x) || !al16(w) || !al16(y) || (reinterpret_cast<uintptr_t>(bias) & 7) || (reinterpret_cast<uintptr_t>(residual) & 7)) {
+        set_error("conv3x3: x, w, y must be 16-byte aligned, bias and residual 8-byte aligned");
+        return PWW_EINVAL;
+    }
+    if (p.nsplit > 1 && (!workspace || !al16(workspace) || workspace_bytes < (size_t)p.nsplit * p.M * d->Cout * sizeof(float))) {
+        set_error("conv3x3: split %d needs a 16-byte aligned workspace of %zu bytes (got %zu)", p.nsplit, (size_t)p.nsplit * p.M * d->Cout * sizeof(float),
+                  workspace_bytes);
+        return PWW_EINVAL;
+    }
+    if (!arch_ok()) return PWW_ENOTSUP;
+    if (d->dtype == PWW_DTYPE_F16) return conv_launch<f16>(p, d, x, w, bias, residual, y, workspace, stream);
+    return conv_launch<bf16>(p, d, x, w, bias, residual, y, workspace, stream);
+}
+
+}  // namespace pww

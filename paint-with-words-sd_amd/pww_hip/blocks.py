@@ -41,6 +41,7 @@ CONV1X1_AS_LINEAR = os.environ.get("PWW_CONV1X1_AS_LINEAR", "1") != "0"  # A/B: 
 # `ff(norm3(h)) + h` through the output GEMM's C operand (no add launch): built in round 5, measured NEUTRAL on the headline (4.04 / 4.06 vs 4.08 /
 # 4.06 images/s, profiles/r05_blocks_ab.md: hipBLASLt's beta = 1 kernels cost what the add launch saves) -> opt-in, off by default
 FUSE_FF_RESIDUAL = os.environ.get("PWW_FUSE_FF_RESIDUAL", "0") == "1"
+CONV3X3 = os.environ.get("PWW_CONV3X3", "1") != "0"      # A/B: 3 x 3 convolutions on channels_last tensors on the HIP implicit-GEMM kernel
 
 
 # ---- what the plug did with the calls it saw (a call the kernels decline must not go unnoticed) ----------------
@@ -48,15 +49,17 @@ FUSE_FF_RESIDUAL = os.environ.get("PWW_FUSE_FF_RESIDUAL", "0") == "1"
 # passes and while a hipGraph is captured (a replay runs no Python). `stats()` returns a copy, `reset_stats()` zeroes; the first decline of
 # a HIP half-precision tensor per (op, reason) also warns once -- under torch.autocast, the reference's own run mode, the whole plug steps
 # aside (autocast runs the norms in fp32) and that is worth knowing when a benchmark claims the fused blocks.
-_STATS = {k: [0, 0] for k in ("group_norm", "resnet_block", "transformer_block", "geglu", "conv1x1")}
+_STATS = {k: [0, 0] for k in ("group_norm", "resnet_block", "transformer_block", "geglu", "conv1x1", "conv3x3")}
+_UNRATED = ("conv1x1", "conv3x3")
 _warned = set()
 
 
 def stats():
     """{op: {"fused": n, "declined": n}} since the last reset_stats(), and the hit rate over the norm / elementwise ops (the 1 x 1
-    convolutions are listed but not rated: an NCHW tensor keeps MIOpen's convolution by the caller's choice of memory format)."""
+    and 3 x 3 convolutions are listed but not rated: an NCHW tensor keeps MIOpen's convolution by the caller's choice of memory format, and
+    the UNet's conv_in / conv_out have channel counts the kernel has no tile for)."""
     out = {k: {"fused": v[0], "declined": v[1]} for k, v in _STATS.items()}
-    rated = [v for k, v in _STATS.items() if k != "conv1x1"]
+    rated = [v for k, v in _STATS.items() if k not in _UNRATED]
     tot = sum(v[0] + v[1] for v in rated)
     out["hit_rate"] = (sum(v[0] for v in rated) / tot) if tot else None
     return out
@@ -192,7 +195,10 @@ def _resnet_forward(self, *args, **kwargs):
     _count("resnet_block", True)
     fold = FOLD_CONV_BIAS and _plain_conv(self.conv1) and _plain_conv(self.conv2) and self.conv1.bias.dtype == input_tensor.dtype
     h = fused_group_norm(self.norm1, input_tensor, act="silu")
-    h = _conv_no_bias(self.conv1, h) if fold else self.conv1(h)
+    if fold and _conv3x3_route(self.conv1, h):
+        h = ops.conv3x3(h, self.conv1.weight)
+    else:
+        h = _conv_no_bias(self.conv1, h) if fold else self.conv1(h)
     add = None
     if temb is not None and getattr(self, "time_emb_proj", None) is not None:
         slot = self.__dict__.get("_pww_temb_slot")
@@ -214,11 +220,59 @@ def _resnet_forward(self, *args, **kwargs):
     if getattr(self, "conv_shortcut", None) is not None:
         input_tensor = self.conv_shortcut(input_tensor)
     scale = getattr(self, "output_scale_factor", 1.0)
-    if fold and input_tensor.dtype == h.dtype and input_tensor.shape[1] % 8 == 0:
+    if fold and input_tensor.dtype == h.dtype and input_tensor.shape == (h.shape[0], self.conv2.out_channels) + h.shape[2:] and _conv3x3_route(self.conv2, h):
+        out = ops.conv3x3(h, self.conv2.weight, self.conv2.bias, residual=input_tensor)           # input + (conv2(h) + bias): one kernel
+    elif fold and input_tensor.dtype == h.dtype and input_tensor.shape[1] % 8 == 0:
         out = ops.bias_residual(input_tensor, _conv_no_bias(self.conv2, h), self.conv2.bias)          # input + (conv2(h) + bias): one launch
     else:
         out = input_tensor + self.conv2(h)
     return out if scale == 1.0 else out / scale
+
+
+# ---- 3 x 3 convolutions on channels_last tensors: the implicit-GEMM kernel of csrc/pww_conv.hip ----------------------------------------
+def _is_conv3x3(m):
+    return (isinstance(m, nn.Conv2d) and type(m).forward is nn.Conv2d.forward and m.kernel_size == (3, 3) and m.stride in ((1, 1), (2, 2))
+            and m.padding == (1, 1) and m.dilation == (1, 1) and m.groups == 1 and m.padding_mode == "zeros")
+
+
+# Output rows (B Ho Wo) from which MIOpen's own kernel is the faster one for a convolution without a fused upsample: the 64 x 64 and 32 x 32
+# levels at batch 8 (16 rows) measured at 0.6 - 0.9x of stock speed on the HIP kernel (profiles/conv3x3_sweep.md); with the upsample fused it wins there too.
+STOCK_FROM_ROWS = 16384
+
+
+def _conv3x3_route(conv, x, upsample=False):
+    """Whether this call of the 3 x 3 `conv` runs on the HIP kernel; counts the call either way (not rated: see stats())."""
+    ok = (CONV3X3 and FUSED_NORM and torch.is_tensor(x) and x.dim() == 4 and _is_conv3x3(conv) and not torch.is_autocast_enabled() and not (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad))
+          and (conv.bias is None or conv.bias.dtype == x.dtype) and ops.conv3x3_takes(x, conv.weight, conv.stride[0], upsample)
+          and (upsample or x.shape[0] * ((x.shape[2] - 1) // conv.stride[0] + 1) * ((x.shape[3] - 1) // conv.stride[0] + 1) < STOCK_FROM_ROWS))
+    _STATS["conv3x3"][0 if ok else 1] += 1
+    return ok
+
+
+def _conv3x3_forward(self, x, *args, **kwargs):
+    if not args and not kwargs and _conv3x3_route(self, x):
+        return ops.conv3x3(x, self.weight, self.bias, stride=self.stride[0])
+    return self._pww_orig_forward(x, *args, **kwargs)
+
+
+def _upsample_conv(m):
+    """The 3 x 3 conv of an ``Upsample2D`` whose forward is nearest-2x interpolate -> conv (diffusers 0.10.0: ``use_conv`` and not
+    ``use_conv_transpose``; the conv is ``conv`` or ``Conv2d_0`` by ``name``), else None."""
+    if getattr(m, "use_conv_transpose", False) or not getattr(m, "use_conv", True):
+        return None
+    conv = getattr(m, "Conv2d_0", None) if getattr(m, "name", "conv") != "conv" else getattr(m, "conv", None)
+    return conv if _is_conv3x3(conv) and conv.stride == (1, 1) and "forward" not in conv.__dict__ and not conv._forward_hooks and not conv._forward_pre_hooks else None
+
+
+def _upsample_forward(self, *args, **kwargs):
+    """diffusers 0.10.0 ``Upsample2D.forward(hidden_states, output_size=None)`` with the nearest-2x interpolation fused into the conv's gather
+    (exact: nearest only copies). An explicit ``output_size``, or anything else, reaches the module's own forward."""
+    plain = 1 <= len(args) <= 2 and set(kwargs) <= {"output_size"} and all(a is None for a in list(args[1:]) + list(kwargs.values()))
+    x = args[0] if plain and not (len(args) == 2 and kwargs) else None
+    conv = _upsample_conv(self)
+    if x is not None and conv is not None and x.dim() == 4 and (getattr(self, "channels", None) in (None, x.shape[1])) and _conv3x3_route(conv, x, upsample=True):
+        return ops.conv3x3(x, conv.weight, conv.bias, upsample=True)
+    return self._pww_orig_forward(*args, **kwargs)
 
 
 # ---- 1 x 1 convolutions on channels_last tensors are GEMMs over the [B H W, C] view: bias in the GEMM's epilogue, no layout kernels ----
@@ -326,7 +380,7 @@ def install_blocks(unet):
                 lin = getattr(m, "time_emb_proj", None)
                 if BATCHED_TEMB and isinstance(lin, nn.Linear):
                     m.__dict__["_pww_temb_slot"] = plans.setdefault(lin.in_features, TembProjections()).register(m)
-            owned.update((id(m.norm1), id(m.norm2)))
+            owned.update((id(m.norm1), id(m.norm2), id(m.conv1), id(m.conv2)))
             n_res += 1
     for m in unet.modules():
         name, fwd = m.__class__.__name__, None
@@ -339,6 +393,11 @@ def install_blocks(unet):
             fwd = _geglu_forward
         elif _is_conv1x1(m):
             fwd = _conv1x1_forward
+        elif name == "Upsample2D" and _upsample_conv(m) is not None:
+            fwd = _upsample_forward
+            owned.add(id(_upsample_conv(m)))
+        elif _is_conv3x3(m) and id(m) not in owned:
+            fwd = _conv3x3_forward
         if fwd is not None and "_pww_orig_forward" not in m.__dict__:
             m.__dict__["_pww_orig_forward"] = m.forward
             m.forward = types.MethodType(fwd, m)

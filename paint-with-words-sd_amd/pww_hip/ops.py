@@ -803,3 +803,59 @@ def bias_residual(residual, value, bias):
         _lib.check(_lib.load().pww_bias_residual(_ptr(residual), _ptr(value), _ptr(bias.contiguous()), _ptr(y), B, C, H * W, layout, _DT[value.dtype], _stream()),
                    "pww_bias_residual")
     return y
+
+
+def _khwc_weight(weight):
+    """The [Cout][3][3][Cin] storage the conv kernel reads: a channels_last weight IS that storage; any other layout gets a repacked copy, cached
+    on the parameter and rebuilt when it was replaced, modified in place (version counter), moved or cast."""
+    if weight.is_contiguous(memory_format=torch.channels_last):
+        return weight
+    key = (weight.data_ptr(), weight._version, weight.dtype, weight.device)
+    hit = weight.__dict__.get("_pww_khwc")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    packed = weight.detach().permute(0, 2, 3, 1).contiguous()
+    weight.__dict__["_pww_khwc"] = (key, packed)
+    return packed
+
+
+def conv3x3_takes(x, weight, stride=1, upsample=False):
+    """True when pww_conv3x3_fwd runs this call: a channels_last 4-d float16 / bfloat16 x on a HIP device, a [Cout, Cin, 3, 3] weight of its dtype,
+    Cin and Cout multiples of 64, stride 1 or 2 (upsample: stride 1)."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in _DT and torch.is_tensor(weight) and weight.dtype == x.dtype and weight.dim() == 4):
+        return False
+    B, C, H, W = x.shape
+    Cout = weight.shape[0]
+    return (tuple(weight.shape[1:]) == (C, 3, 3) and C % 64 == 0 and Cout % 64 == 0 and stride in (1, 2) and not (upsample and stride != 1)
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0
+            and B * H * W * C < 2 ** 31 // 4)
+
+
+def conv3x3(x, weight, bias=None, residual=None, stride=1, upsample=False, tile_n=0, splitk=0):
+    """3 x 3 convolution, padding 1, of a channels_last x ([B, Cin, H, W]) -> channels_last [B, Cout, Ho, Wo] on one HIP implicit-GEMM kernel
+    (+ a fold launch when the K dimension is split). upsample: the input is first upsampled 2x nearest (fused into the gather). Epilogue with
+    the stock roundings: T(residual + T(T(conv) + bias)), each term when given. tile_n / splitk: 0 = the library's choice (A/B and tools)."""
+    _require_gpu(x, weight, bias, residual)
+    if not conv3x3_takes(x, weight, stride, upsample):
+        raise PwwHipError("conv3x3: needs a channels_last float16/bfloat16 x with Cin, Cout multiples of 64 and a 3 x 3 weight of its dtype")
+    B, C, H, W = x.shape
+    Cout = weight.shape[0]
+    Hv, Wv = H << int(bool(upsample)), W << int(bool(upsample))
+    Ho, Wo = (Hv - 1) // stride + 1, (Wv - 1) // stride + 1
+    w = _khwc_weight(weight)
+    if bias is not None and (bias.dtype != x.dtype or tuple(bias.shape) != (Cout,)):
+        raise PwwHipError("conv3x3: bias must be a %s [%d]" % (x.dtype, Cout))
+    if bias is not None:
+        bias = bias.contiguous()
+    if residual is not None:
+        if tuple(residual.shape) != (B, Cout, Ho, Wo) or residual.dtype != x.dtype:
+            raise PwwHipError("conv3x3: residual must be a %s %s" % (x.dtype, (B, Cout, Ho, Wo)))
+        residual = residual.contiguous(memory_format=torch.channels_last)
+    d = _lib.ConvDesc(ctypes.sizeof(_lib.ConvDesc), _DT[x.dtype], B, H, W, C, Cout, int(stride), int(bool(upsample)), int(tile_n), int(splitk), 0)
+    lib = _lib.load()
+    y = torch.empty((B, Cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    nbytes = int(lib.pww_conv3x3_workspace_bytes(ctypes.byref(d)))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    with torch.cuda.device(x.device):
+        _lib.check(lib.pww_conv3x3_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(y), ctypes.byref(d), _ptr(ws), nbytes, _stream()), "pww_conv3x3_fwd")
+    return y
