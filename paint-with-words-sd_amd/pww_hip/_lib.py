@@ -91,6 +91,10 @@ _exp = None
 def _bind(lib, experiments):
     vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
     lib.pww_version.restype = ctypes.c_int
+    # first of all: an older library lacks symbols that are bound below, and has to end here with the rebuild hint
+    if lib.pww_version() // 100 != 1 or lib.pww_version() < MIN_VERSION:
+        raise PwwHipError("libpww_hip ABI version %d.%02d is not 1.x >= 1.%02d (rebuild: python paint-with-words-sd_amd/build.py)"
+                          % (lib.pww_version() // 100, lib.pww_version() % 100, MIN_VERSION % 100))
     lib.pww_last_error.restype = ctypes.c_char_p
     lib.pww_device_arch.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     lib.pww_self_attn_fwd.argtypes = [vp, vp, vp, vp, ctypes.POINTER(AttnDesc), vp]
@@ -151,9 +155,6 @@ def _bind(lib, experiments):
     for name in ("pww_device_arch", "pww_self_attn_fwd", "pww_cross_attn_fwd", "pww_cross_attn_fwd_stat", "pww_cross_attn_fwd_stat_ex", "pww_qk_reduce",
                  "pww_mask_build", "pww_mask_build_rgb", "pww_mask_build_f32", "pww_resize_tokens", "pww_gauss_blur", "pww_inpaint_prep", "pww_cfg_combine"):
         getattr(lib, name).restype = ctypes.c_int
-    if lib.pww_version() // 100 != 1 or lib.pww_version() < MIN_VERSION:
-        raise PwwHipError("libpww_hip ABI version %d.%02d is not 1.x >= 1.%02d (rebuild: python paint-with-words-sd_amd/build.py)"
-                          % (lib.pww_version() // 100, lib.pww_version() % 100, MIN_VERSION % 100))
     lib.pww_has_experiments.restype = ctypes.c_int
     if experiments:
         lib.pww_cross_attn_fwd_fused.argtypes = [vp, vp, vp, vp, vp, i32, f32, vp, ctypes.POINTER(AttnDesc), vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]
@@ -183,8 +184,8 @@ def load():
             "libpww_hip.so not found at %s. Build it with `python paint-with-words-sd_amd/build.py` "
             "(or __graft_entry__.build()). There is no CPU/PyTorch fallback for the PwW kernels." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    lib.pww_has_experiments.restype = ctypes.c_int
-    _lib = _bind(lib, bool(lib.pww_has_experiments()) if hasattr(lib, "pww_has_experiments") else False)
+    # (a library from before pww_has_experiments -- an int function, ctypes' default -- is too old: _bind's version check says so)
+    _lib = _bind(lib, hasattr(lib, "pww_has_experiments") and bool(lib.pww_has_experiments()))
     return _lib
 
 
@@ -194,7 +195,7 @@ def has_experiments():
 
 
 def load_experiments():
-    """libpww_hip_experiments.so (test / tool infrastructure: round 3's in-launch statistic, the attention + to_out launch, the A/B kernels
+    """libpww_hip_experiments.so (test / tool infrastructure: the statistic formed inside the attention launch, the attention + to_out launch, the A/B kernels
     behind PWW_DEBUG). The product never calls this; a missing library raises with the build command."""
     global _exp
     if _exp is not None:

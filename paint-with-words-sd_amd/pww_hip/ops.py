@@ -68,9 +68,8 @@ def _prep(t):
 
 
 STAT_NONE, STAT_MAX, STAT_MIN, STAT_MEAN, STAT_STD, STAT_ABSMAX, STAT_ALL = 0, 1, 2, 3, 4, 5, 6   # PWW_STAT_* of include/pww_hip.h
-
-
 FUSED_MAX_KEYS = 128   # pww_cross_attn_fwd_fused: one K/V stage
+COMPACT_MAX_R = 32     # pww_cross.hip: the compact form holds at most 32 non-zero columns
 
 
 class FusedScratch:
@@ -188,8 +187,9 @@ def check_fused_errors(modules):
         raise PwwHipError(_TIMEOUT_MESSAGE)
 
 
-def _cross_opts(B, N, coeff_dev, bias_cols, compact, keep, gated=0):
-    """pww_cross_opts_t for the *_ex entry points (None if nothing optional is asked for)."""
+def _cross_opts(B, N, coeff_dev, bias_cols, compact, gated=0):
+    """pww_cross_opts_t for the *_ex entry points (None if nothing optional is asked for). The struct holds device addresses, not
+    references: the compact views made here ride on it as `op.keep`, so they live as long as the caller holds the struct."""
     if coeff_dev is None and not bias_cols and compact is None and not gated:
         return None
     op = CrossOpts()
@@ -214,11 +214,99 @@ def _cross_opts(B, N, coeff_dev, bias_cols, compact, keep, gated=0):
         op.bias_compact, op.col_idx, op.R = wc.data_ptr(), idx.data_ptr(), R
         op.compact_stride[:] = [wc.stride(0) if wc.shape[0] == B and B > 1 else 0, wc.stride(1)]
         op.col_idx_stride = idx.stride(0) if idx.shape[0] == B and B > 1 else 0
-        keep.extend([wc, idx])
+        op.keep = (wc, idx)
     return op
 
 
-COMPACT_MAX_R = 32     # pww_cross.hip: the compact form holds at most 32 non-zero columns
+def _opt_ref(op):
+    return ctypes.byref(op) if op is not None else None
+
+
+def _bias_view(bias, d):
+    """The fp32 [B, heads, N, M] view of a bias that broadcasts to it, its strides entered into the descriptor."""
+    if bias.dtype != torch.float32:
+        bias = bias.float()
+    if bias.dim() == 3 and bias.shape[0] == d.B * d.H and d.B * d.H != 1:
+        bias = bias.reshape(d.B, d.H, bias.shape[1], bias.shape[2])
+    bias = torch.broadcast_to(bias, (d.B, d.H, d.N, d.M))  # view: broadcast axes get stride 0
+    d.bias_stride[:] = list(bias.stride())
+    return bias
+
+
+def _per_image_f32(t, B, name, expand=False):
+    """None, or `t` as the contiguous fp32 [B] vector the kernels read; expand: a single element serves every image."""
+    if t is None:
+        return None
+    t = t.to(torch.float32).reshape(-1).contiguous()
+    if expand and t.numel() == 1 and B > 1:
+        t = t.expand(B).contiguous()
+    if t.numel() != B:
+        raise PwwHipError("%s must have B=%d elements" % (name, B))
+    return t
+
+
+def _check_f64(t, name, *shape):
+    """`t` is None or a contiguous float64 tensor of `shape` = (B, ...); an extent given as a string is free and named by it."""
+    if t is not None and (t.dtype != torch.float64 or t.dim() != len(shape) or not t.is_contiguous()
+                          or any(not isinstance(s, str) and s != n for s, n in zip(shape, t.shape))):
+        raise PwwHipError("%s must be a contiguous float64 [%s] tensor" % (name, ", ".join(["B"] + [str(s) for s in shape[1:]])))
+
+
+def _attention_route(has_bias, stat, scratch, parts, M):
+    """The launch attention() takes, decided from which arguments are given and the key count alone (no tensor is touched)."""
+    if not has_bias:
+        return "self"       # pww_self_attn_fwd
+    if stat is None:
+        return "plain"      # pww_cross_attn_fwd: c[b] = bias_coeff[b]
+    if stat[0] is not None:
+        return "stat"       # pww_cross_attn_fwd_stat_ex: the [B, 4] statistics of qk_stats come with the call
+    if stat[1] == STAT_NONE and parts is None and M > FUSED_MAX_KEYS:
+        return "stat"       # ... with null stats: nothing to form or fold, and only this launch has no key limit (scratch or not)
+    # stat = (None, kind, scalar): partials folded at entry (pww_cross_attn_fwd_parts), or, with a FusedScratch, the statistic formed in
+    # the launch (pww_cross_attn_fwd_fused_ex, experiments library)
+    return "parts" if scratch is None else "fused"
+
+
+def _launch_stat(lib, io, bias, coeff, d, stat, coeff_dev):
+    """c[b] = scalar * stat(stats[b]) * coeff[b]; null stats (STAT_NONE): the scalar -- or the hipGraph mode's device word -- alone."""
+    stats, kind, scalar = stat
+    _check_f64(stats, "stat: stats", d.B, 4)
+    op = _cross_opts(d.B, d.N, coeff_dev, 0, None)
+    _lib.check(lib.pww_cross_attn_fwd_stat_ex(*io, _ptr(bias), _ptr(stats), int(kind), float(d.H * d.N * d.M), float(scalar), _ptr(coeff),
+                                              ctypes.byref(d), _opt_ref(op), _stream()), "pww_cross_attn_fwd_stat_ex")
+
+
+def _launch_parts(lib, io, bias, coeff, d, stat, parts, stats_out, coeff_dev, bias_cols, compact, gated):
+    """Pass 2 only: the statistic's partials came from qproj_stat / qk_parts (none needed for STAT_NONE); nothing in it waits for another workgroup."""
+    _, kind, scalar = stat
+    if kind != STAT_NONE and parts is None:
+        raise PwwHipError("a statistic formed outside the attention launch needs its partials (qproj_stat / qk_parts), or a FusedScratch for the in-launch form")
+    _check_f64(parts, "parts", d.B, "nparts", 4)
+    if d.M > FUSED_MAX_KEYS:
+        raise PwwHipError("the pass-2-only cross-attention launch takes at most %d keys (partials over more keys: fold them with "
+                          "fold_parts and pass stat=(stats, kind, scalar))" % FUSED_MAX_KEYS)
+    _check_f64(stats_out, "stats_out", d.B, 4)
+    if compact is not None and (compact[0].shape[-1] > COMPACT_MAX_R or not _lib.has_experiments()):
+        compact = None          # (the compact form of the map is an experiments-library form: the dense map serves)
+    op = _cross_opts(d.B, d.N, coeff_dev, bias_cols, compact, gated)
+    _lib.check(lib.pww_cross_attn_fwd_parts(*io, _ptr(bias), int(kind), float(scalar), _ptr(coeff), ctypes.byref(d), _ptr(parts),
+                                            int(parts.shape[1]) if parts is not None else 0, _ptr(stats_out), _opt_ref(op), _stream()),
+               "pww_cross_attn_fwd_parts")
+
+
+def _launch_fused(io, bias, coeff, d, stat, scratch, device, stats_out, coeff_dev, bias_cols, compact, gated):
+    """The statistic formed in the attention launch itself, through the workgroup hand-off in `scratch`: not part of the product library."""
+    _, kind, scalar = stat
+    if d.M > FUSED_MAX_KEYS:
+        raise PwwHipError("fused statistic needs a FusedScratch and at most %d keys" % FUSED_MAX_KEYS)
+    xlib = _lib.load_experiments()
+    state, ws = scratch.ensure(xlib, d, device)
+    _check_f64(stats_out, "stats_out", d.B, 4)
+    if compact is not None and compact[0].shape[-1] > COMPACT_MAX_R:
+        compact = None
+    op = _cross_opts(d.B, d.N, coeff_dev, bias_cols, compact, gated)
+    _lib.check(xlib.pww_cross_attn_fwd_fused_ex(*io, _ptr(bias), int(kind), float(scalar), _ptr(coeff), ctypes.byref(d), _ptr(stats_out), _ptr(state),
+                                                state.numel() * 8, _ptr(ws), ws.numel() * 8, _opt_ref(op), _stream()), "pww_cross_attn_fwd_fused_ex", xlib)
 
 
 def attention(q, k, v, heads, scale, bias=None, bias_coeff=None, stat=None, scratch=None, stats_out=None, coeff_dev=None,
@@ -240,95 +328,26 @@ def attention(q, k, v, heads, scale, bias=None, bias_coeff=None, stat=None, scra
         raise PwwHipError("q/k/v dtypes differ: %s %s %s" % (q.dtype, k.dtype, v.dtype))
     q, k, v = _prep(q), _prep(k), _prep(v)
     B, N, C = q.shape
-    M = k.shape[1]
     out = torch.empty((B, N, C), dtype=q.dtype, device=q.device)
     d = _desc(q, k, v, out, heads, scale)
     lib = _lib.load()
+    route = _attention_route(bias is not None, stat, scratch, parts, d.M)
+    io = (_ptr(q), _ptr(k), _ptr(v), _ptr(out))
+    if route != "self":
+        bias = _bias_view(bias, d)
+        bias_coeff = _per_image_f32(bias_coeff, B, "bias_coeff", expand=True)
     with torch.cuda.device(q.device):
-        if bias is None:
-            rc = lib.pww_self_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), ctypes.byref(d), _stream())
-            _lib.check(rc, "pww_self_attn_fwd")
+        if route == "self":
+            _lib.check(lib.pww_self_attn_fwd(*io, ctypes.byref(d), _stream()), "pww_self_attn_fwd")
+        elif route == "plain":
+            _lib.check(lib.pww_cross_attn_fwd(*io, _ptr(bias), _ptr(bias_coeff), ctypes.byref(d), _stream()), "pww_cross_attn_fwd")
+        elif route == "stat":
+            _launch_stat(lib, io, bias, bias_coeff, d, stat, coeff_dev)
+        elif route == "parts":
+            _launch_parts(lib, io, bias, bias_coeff, d, stat, parts, stats_out, coeff_dev, bias_cols, compact, gated)
         else:
-            if bias.dtype != torch.float32:
-                bias = bias.float()
-            if bias.dim() == 3 and bias.shape[0] == B * heads and B * heads != 1:
-                bias = bias.reshape(B, heads, bias.shape[1], bias.shape[2])
-            bias = torch.broadcast_to(bias, (B, heads, N, M))  # view: broadcast axes get stride 0
-            d.bias_stride[:] = list(bias.stride())
-            if bias_coeff is not None:
-                bias_coeff = bias_coeff.to(torch.float32).reshape(-1).contiguous()
-                if bias_coeff.numel() == 1 and B > 1:
-                    bias_coeff = bias_coeff.expand(B).contiguous()
-                if bias_coeff.numel() != B:
-                    raise PwwHipError("bias_coeff must have B=%d elements" % B)
-            if stat is not None and stat[0] is None and stat[1] == STAT_NONE and parts is None and M > FUSED_MAX_KEYS:
-                # a statistic-free weight function over a context longer than one K/V stage: nothing to fold, nothing to form -- the
-                # general launch (no key limit) with its scalar (or the hipGraph mode's device word) as the coefficient
-                _, kind, scalar = stat
-                op = _cross_opts(B, N, coeff_dev, 0, None, [])
-                rc = lib.pww_cross_attn_fwd_stat_ex(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(bias), None, int(STAT_NONE),
-                                                    float(heads * N * M), float(scalar), _ptr(bias_coeff), ctypes.byref(d),
-                                                    ctypes.byref(op) if op is not None else None, _stream())
-                _lib.check(rc, "pww_cross_attn_fwd_stat_ex")
-            elif stat is not None and stat[0] is None and scratch is None:
-                # pass-2-only launch: the statistic's partials came from qproj_stat / qk_parts (none needed for STAT_NONE); nothing in it
-                # waits for another workgroup
-                _, kind, scalar = stat
-                if kind != STAT_NONE and parts is None:
-                    raise PwwHipError("a statistic formed outside the attention launch needs its partials (qproj_stat / qk_parts), or a FusedScratch for the in-launch form")
-                if parts is not None and (parts.dtype != torch.float64 or parts.dim() != 3 or parts.shape[0] != B or parts.shape[2] != 4 or not parts.is_contiguous()):
-                    raise PwwHipError("parts must be a contiguous float64 [B, nparts, 4] tensor")
-                if M > FUSED_MAX_KEYS:
-                    raise PwwHipError("the pass-2-only cross-attention launch takes at most %d keys (partials over more keys: fold them with "
-                                      "fold_parts and pass stat=(stats, kind, scalar))" % FUSED_MAX_KEYS)
-                if stats_out is not None and (stats_out.dtype != torch.float64 or tuple(stats_out.shape) != (B, 4) or not stats_out.is_contiguous()):
-                    raise PwwHipError("stats_out must be a contiguous float64 [B, 4] tensor")
-                keep = []
-                if compact is not None and (compact[0].shape[-1] > COMPACT_MAX_R or not _lib.has_experiments()):
-                    compact = None          # (the compact form of the map is an experiments-library form: the dense map serves)
-                op = _cross_opts(B, N, coeff_dev, bias_cols, compact, keep, gated)
-                rc = lib.pww_cross_attn_fwd_parts(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(bias), int(kind), float(scalar), _ptr(bias_coeff),
-                                                  ctypes.byref(d), _ptr(parts), int(parts.shape[1]) if parts is not None else 0, _ptr(stats_out),
-                                                  ctypes.byref(op) if op is not None else None, _stream())
-                _lib.check(rc, "pww_cross_attn_fwd_parts")
-            elif stat is not None and stat[0] is None:
-                _, kind, scalar = stat
-                if M > FUSED_MAX_KEYS:
-                    raise PwwHipError("fused statistic needs a FusedScratch and at most %d keys" % FUSED_MAX_KEYS)
-                xlib = _lib.load_experiments()      # round 3's in-launch statistic is not part of the product library
-                state, ws = scratch.ensure(xlib, d, q.device)
-                if stats_out is not None and (stats_out.dtype != torch.float64 or tuple(stats_out.shape) != (B, 4) or not stats_out.is_contiguous()):
-                    raise PwwHipError("stats_out must be a contiguous float64 [B, 4] tensor")
-                keep = []
-                if compact is not None and compact[0].shape[-1] > COMPACT_MAX_R:
-                    compact = None
-                op = _cross_opts(B, N, coeff_dev, bias_cols, compact, keep, gated)
-                rc = xlib.pww_cross_attn_fwd_fused_ex(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(bias), int(kind), float(scalar),
-                                                      _ptr(bias_coeff), ctypes.byref(d), _ptr(stats_out), _ptr(state), state.numel() * 8,
-                                                      _ptr(ws), ws.numel() * 8, ctypes.byref(op) if op is not None else None, _stream())
-                _lib.check(rc, "pww_cross_attn_fwd_fused_ex", xlib)
-            elif stat is not None:
-                stats, kind, scalar = stat
-                if stats is not None and (stats.dtype != torch.float64 or tuple(stats.shape) != (B, 4) or not stats.is_contiguous()):
-                    raise PwwHipError("stat: stats must be a contiguous float64 [B, 4] tensor")
-                op = _cross_opts(B, N, coeff_dev, 0, None, [])
-                rc = lib.pww_cross_attn_fwd_stat_ex(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(bias), _ptr(stats), int(kind),
-                                                    float(heads * N * M), float(scalar), _ptr(bias_coeff), ctypes.byref(d),
-                                                    ctypes.byref(op) if op is not None else None, _stream())
-                _lib.check(rc, "pww_cross_attn_fwd_stat_ex")
-            else:
-                rc = lib.pww_cross_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(bias), _ptr(bias_coeff),
-                                            ctypes.byref(d), _stream())
-                _lib.check(rc, "pww_cross_attn_fwd")
+            _launch_fused(io, bias, bias_coeff, d, stat, scratch, q.device, stats_out, coeff_dev, bias_cols, compact, gated)
     return out
-
-
-def _bias_view(bias, B, heads, N, M):
-    if bias.dtype != torch.float32:
-        bias = bias.float()
-    if bias.dim() == 3 and bias.shape[0] == B * heads and B * heads != 1:
-        bias = bias.reshape(B, heads, bias.shape[1], bias.shape[2])
-    return torch.broadcast_to(bias, (B, heads, N, M))  # view: broadcast axes get stride 0
 
 
 def attention_out_supported(q, k, heads, bias, weight, bias_cols=0):
@@ -340,15 +359,14 @@ def attention_out_supported(q, k, heads, bias, weight, bias_cols=0):
     M = k.shape[1]
     if tuple(weight.shape) != (C, C) or weight.dtype != q.dtype or not weight.is_contiguous() or C % heads:
         return False
-    try:
-        bv = _bias_view(bias, B, heads, N, M)
-    except RuntimeError:
-        return False
     d = AttnDesc()
     d.dtype = _DT[q.dtype]
     d.B, d.H, d.N, d.M, d.D = B, heads, N, M, C // heads
     d.q_stride[:] = [q.stride(0), C // heads, q.stride(1)]
-    d.bias_stride[:] = list(bv.stride())
+    try:
+        _bias_view(bias, d)
+    except RuntimeError:
+        return False
     return bool(_lib.load_experiments().pww_cross_attn_out_supported(ctypes.byref(d), C, int(bias_cols)))
 
 
@@ -365,7 +383,6 @@ def attention_out(q, k, v, heads, scale, bias, weight, weight_bias=None, residua
         raise PwwHipError("q/k/v/weight dtypes differ: %s %s %s %s" % (q.dtype, k.dtype, v.dtype, weight.dtype))
     q, k, v = _prep(q), _prep(k), _prep(v)
     B, N, C = q.shape
-    M = k.shape[1]
     if tuple(weight.shape) != (C, C) or not weight.is_contiguous():
         raise PwwHipError("attention_out: weight must be a contiguous [%d, %d] tensor" % (C, C))
     if weight_bias is not None and (weight_bias.dtype != q.dtype or tuple(weight_bias.shape) != (C,) or not weight_bias.is_contiguous()):
@@ -374,31 +391,22 @@ def attention_out(q, k, v, heads, scale, bias, weight, weight_bias=None, residua
         raise PwwHipError("attention_out: residual must be a [B, N, C] tensor of q's dtype with unit channel stride")
     out = torch.empty((B, N, C), dtype=q.dtype, device=q.device)
     d = _desc(q, k, v, out, heads, scale)
-    bias = _bias_view(bias, B, heads, N, M)
-    d.bias_stride[:] = list(bias.stride())
-    if bias_coeff is not None:
-        bias_coeff = bias_coeff.to(torch.float32).reshape(-1).contiguous()
-        if bias_coeff.numel() == 1 and B > 1:
-            bias_coeff = bias_coeff.expand(B).contiguous()
-        if bias_coeff.numel() != B:
-            raise PwwHipError("bias_coeff must have B=%d elements" % B)
+    bias = _bias_view(bias, d)
+    bias_coeff = _per_image_f32(bias_coeff, B, "bias_coeff", expand=True)
     kind, scalar = (STAT_NONE, 1.0) if stat is None else (stat[1], stat[2])
     if stat is not None and stat[0] is not None:
         raise PwwHipError("attention_out folds partials (stat = (None, kind, scalar), parts = qproj_stat / qk_parts output)")
     if kind != STAT_NONE and parts is None:
         raise PwwHipError("attention_out: a statistic needs its partials (qproj_stat / qk_parts)")
-    if parts is not None and (parts.dtype != torch.float64 or parts.dim() != 3 or parts.shape[0] != B or parts.shape[2] != 4 or not parts.is_contiguous()):
-        raise PwwHipError("parts must be a contiguous float64 [B, nparts, 4] tensor")
-    if stats_out is not None and (stats_out.dtype != torch.float64 or tuple(stats_out.shape) != (B, 4) or not stats_out.is_contiguous()):
-        raise PwwHipError("stats_out must be a contiguous float64 [B, 4] tensor")
-    keep = []
-    op = _cross_opts(B, N, coeff_dev, bias_cols, None, keep, gated)
+    _check_f64(parts, "parts", B, "nparts", 4)
+    _check_f64(stats_out, "stats_out", B, 4)
+    op = _cross_opts(B, N, coeff_dev, bias_cols, None, gated)
     rs = (ctypes.c_int64 * 2)(residual.stride(0), residual.stride(1)) if residual is not None else None
     lib = _lib.load_experiments()
     with torch.cuda.device(q.device):
         rc = lib.pww_cross_attn_fwd_parts_out(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(bias), int(kind), float(scalar), _ptr(bias_coeff), ctypes.byref(d),
                                               _ptr(parts), int(parts.shape[1]) if parts is not None else 0, _ptr(stats_out),
-                                              ctypes.byref(op) if op is not None else None, _ptr(weight), _ptr(weight_bias), _ptr(residual), rs, _stream())
+                                              _opt_ref(op), _ptr(weight), _ptr(weight_bias), _ptr(residual), rs, _stream())
     _lib.check(rc, "pww_cross_attn_fwd_parts_out", lib)
     return out
 
@@ -447,10 +455,7 @@ def qproj_stat(x, weight, k, heads, kind, gate=None):
     if nparts <= 0:
         raise PwwHipError("qproj_stat: unsupported shape (C = %d, head dim %d, Cin = %d): ask qproj_parts() first" % (C, C // heads, Cin))
     parts = torch.empty((B, nparts, 4), dtype=torch.float64, device=x.device)
-    if gate is not None:
-        gate = gate.to(torch.float32).reshape(-1).contiguous()
-        if gate.numel() != B:
-            raise PwwHipError("gate must have B=%d elements" % B)
+    gate = _per_image_f32(gate, B, "gate")
     with torch.cuda.device(x.device):
         _lib.check(lib.pww_qproj_stat(_ptr(x), _ptr(weight), _ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), _ptr(parts),
                                       parts.numel() * 8, _stream()), "pww_qproj_stat")
@@ -473,10 +478,7 @@ def qk_parts(q, k, heads, kind, gate=None, gated=0):
         raise PwwHipError("qk_parts: unsupported problem %s x %s, %d heads" % (tuple(q.shape), tuple(k.shape), heads))
     B = q.shape[0]
     parts = torch.empty((B, nparts, 4), dtype=torch.float64, device=q.device)
-    if gate is not None:
-        gate = gate.to(torch.float32).reshape(-1).contiguous()
-        if gate.numel() != B:
-            raise PwwHipError("gate must have B=%d elements" % B)
+    gate = _per_image_f32(gate, B, "gate")
     with torch.cuda.device(q.device):
         _lib.check(lib.pww_qk_parts(_ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), int(gated or 0), _ptr(parts), parts.numel() * 8, _stream()),
                    "pww_qk_parts")
@@ -706,10 +708,8 @@ def group_norm(x, num_groups, weight=None, bias=None, eps=1e-5, add=None, act=No
                           "groups <= 32, C <= 4096 in channels_last)" % (B, C, H * W, num_groups))
     ws = workspace if workspace is not None else torch.empty(int(need), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.pww_group_norm_fwd(_ptr(x), _ptr(pre_bias) if pre_bias is not None else None, _ptr(add) if add is not None else None,
-                                          _ptr(weight) if weight is not None else None,
-                                          _ptr(bias) if bias is not None else None, _ptr(out), ctypes.byref(d), _ptr(ws), ws.numel(), _stream()),
-                   "pww_group_norm_fwd")
+        _lib.check(lib.pww_group_norm_fwd(_ptr(x), _ptr(pre_bias), _ptr(add), _ptr(weight), _ptr(bias), _ptr(out), ctypes.byref(d), _ptr(ws), ws.numel(),
+                                          _stream()), "pww_group_norm_fwd")
     return out
 
 
@@ -759,12 +759,11 @@ def add_layer_norm(x, weight, bias, eps, a=None, post_bias=None):
     d = _lib.LnDesc(_DT[x.dtype], C, rows, ra[2] if ra else 0, xs, C, C, float(eps), 0)
     with torch.cuda.device(x.device):
         if post_bias is not None:
-            _lib.check(_lib.load().pww_add_layer_norm_bias(_ptr(a), _ptr(x), _ptr(weight) if weight is not None else None, _ptr(bias) if bias is not None else None,
-                                                           _ptr(post_bias), _ptr(s), _ptr(y), ctypes.byref(d), _stream()), "pww_add_layer_norm_bias")
+            _lib.check(_lib.load().pww_add_layer_norm_bias(_ptr(a), _ptr(x), _ptr(weight), _ptr(bias), _ptr(post_bias), _ptr(s), _ptr(y), ctypes.byref(d),
+                                                           _stream()), "pww_add_layer_norm_bias")
         else:
-            _lib.check(_lib.load().pww_add_layer_norm(_ptr(a) if a is not None else None, _ptr(x), _ptr(weight) if weight is not None else None,
-                                                      _ptr(bias) if bias is not None else None, _ptr(s) if s is not None else None, _ptr(y),
-                                                      ctypes.byref(d), _stream()), "pww_add_layer_norm")
+            _lib.check(_lib.load().pww_add_layer_norm(_ptr(a), _ptr(x), _ptr(weight), _ptr(bias), _ptr(s), _ptr(y), ctypes.byref(d), _stream()),
+                       "pww_add_layer_norm")
     return (s, y) if a is not None else y
 
 

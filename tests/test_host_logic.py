@@ -869,3 +869,52 @@ def test_fused_projection_entry_point_says_what_it_takes(experiments_lib):
     with pytest.raises(pww_hip.PwwHipError):
         ops.attention_out(x, x[:, :77], x[:, :77], 8, 1.0, torch.rand(128, 77), torch.randn(320, 320).half())
     assert attention.FUSE_TO_OUT is False and not hasattr(_lib.load(), "pww_cross_attn_fwd_parts_out") or _lib.has_experiments()
+
+
+def test_attention_route_table():
+    """ops._attention_route: which launch ops.attention takes, from which arguments are given and the key count alone -- every row of the
+    table in DESIGN.md section 5, the tie-break of the statistic-free long context over the partials / in-launch rows included."""
+    from pww_hip import ops
+    route = ops._attention_route
+    stats, parts, scratch = object(), object(), object()          # stand-ins: the decision looks at `is None` only
+    kinds = (ops.STAT_NONE, ops.STAT_MAX, ops.STAT_STD)
+    for M in (77, 128, 129, 4096):
+        for sc in (None, scratch):
+            for pt in (None, parts):
+                for stat in [None] + [(s, kind, 0.5) for s in (None, stats) for kind in kinds]:
+                    assert route(False, stat, sc, pt, M) == "self"                   # no bias: whatever else is given
+                assert route(True, None, sc, pt, M) == "plain"
+                for kind in kinds:
+                    assert route(True, (stats, kind, 0.5), sc, pt, M) == "stat"      # the statistics come with the call
+    # stat = (None, STAT_NONE, scalar) over more keys than one K/V stage, no partials: the launch without a key limit, scratch or not
+    assert ops.FUSED_MAX_KEYS == 128
+    assert route(True, (None, ops.STAT_NONE, 0.5), None, None, 129) == "stat"
+    assert route(True, (None, ops.STAT_NONE, 0.5), scratch, None, 129) == "stat"
+    # ... and not at 128 keys, not with partials, not with a statistic to form
+    assert route(True, (None, ops.STAT_NONE, 0.5), None, None, 128) == "parts"
+    assert route(True, (None, ops.STAT_NONE, 0.5), scratch, None, 128) == "fused"
+    assert route(True, (None, ops.STAT_NONE, 0.5), None, parts, 129) == "parts"
+    assert route(True, (None, ops.STAT_NONE, 0.5), scratch, parts, 129) == "fused"
+    for M in (77, 128, 129):
+        for pt in (None, parts):
+            assert route(True, (None, ops.STAT_MAX, 0.5), None, pt, M) == "parts"
+            assert route(True, (None, ops.STAT_MAX, 0.5), scratch, pt, M) == "fused"
+
+
+def test_stale_library_fails_with_the_rebuild_hint(monkeypatch, tmp_path):
+    """A libpww_hip.so older than the package (here: ABI 1.25, and none of the symbols added since) ends in PwwHipError with the build
+    command -- not in the AttributeError of the first symbol it lacks."""
+    import pww_hip._lib as L
+
+    class Stale:
+        def __init__(self, path):
+            self.pww_version = lambda: 125
+            self.pww_last_error = lambda: b""
+    so = tmp_path / "libpww_hip.so"
+    so.write_bytes(b"")
+    monkeypatch.setattr(L, "_lib", None)
+    monkeypatch.setattr(L, "LIB_PATH", str(so))
+    monkeypatch.setattr(L.ctypes, "CDLL", Stale)
+    with pytest.raises(L.PwwHipError, match=r"1\.25 .*rebuild: python paint-with-words-sd_amd/build\.py"):
+        L.load()
+    assert L._lib is None
