@@ -13,6 +13,7 @@
  *   pww_qk_reduce        the global reductions weight_function applies to `qk`
  *                        (paint_with_words.py:402-405 qk.max(); README.md:152 qk.std())
  *   pww_cross_attn_fwd_stat  pww_cross_attn_fwd with `c0 * g(sigma) * reduce(qk)` formed in the kernel
+ *   pww_cross_attn_probs paint_with_words/paint_with_words.py:112-114 (`attention_scores.softmax(dim=-1)`, averaged over the heads)
  *   pww_mask_build       paint_with_words/paint_with_words.py:207-276
  *                        (_image_context_seperator + _tokens_img_attention_weight +
  *                         _img_importance_flatten for ratios 8/16/32/64)
@@ -332,6 +333,36 @@ typedef struct pww_conv_desc {
 size_t pww_conv3x3_workspace_bytes(const pww_conv_desc_t *desc);
 int pww_conv3x3_fwd(const void *x, const void *w, const void *bias, const void *residual, void *y, const pww_conv_desc_t *desc, void *workspace,
                     size_t workspace_bytes, void *stream);
+
+/*
+ * Head-averaged softmax probabilities of one cross-attention call over the prompt tokens -- the tensor the reference holds as
+ * `attention_scores.softmax(dim=-1)` (paint_with_words/paint_with_words.py:112-114) and every attention entry point above keeps in registers:
+ *     out[b][n][m] (+)= weight * (1 / H) * sum_h softmax_m( ((Q K^T)[b,h,n,m] + c[b] * bias[b,h,n,m]) * scale )        b < images
+ * A diagnostic launch of its own, issued beside the attention launch of the same call with the same q / k / map / coefficient inputs (the
+ * per-token attention maps of pww_hip.record_attention_maps). No ABI version bump: pww_probs_desc_t carries its own size.
+ *   bias, stats, stat_kind, stat_count, coeff_scalar, gate, opts->coeff_scalar_dev   as in pww_cross_attn_fwd_stat_ex:
+ *             c[b] = coeff_scalar * stat(stats[b]) * (gate ? gate[b] : 1), fp32 products in that order; bias == NULL: plain softmax; stats == NULL
+ *             only with PWW_STAT_NONE. For a pww_cross_attn_fwd call pass its bias_coeff as `gate` (coeff_scalar 1); for pww_cross_attn_fwd_parts
+ *             pass the folded statistics that launch wrote to its `stats_out`. The other fields of `opts` are not read.
+ *   desc      dtype, B / H / N / M / D, q / k / bias strides and scale are read (v_stride, o_stride are not)
+ *   out       fp32, element (b, n, m) at out + b*out_stride[0] + n*out_stride[1] + m, 16-byte aligned; only b < images, n < N, m < M are touched
+ * Supported: M <= 128, D a multiple of 8 up to PWW_MAX_HEAD_DIM, both storage types, any N; PWW_ENOTSUP otherwise. Scores by MFMA with fp32
+ * accumulation from the rounded Q / K the attention kernels read; the softmax is the plain one in fp32 (exact row maximum, exp, exact row sum).
+ * Every output element has ONE owner (a workgroup per 32-row block of an image walks all heads and sums them in a fixed order): no atomics,
+ * results bitwise repeatable, accumulate = 1 is a read-modify-write by that owner (calls that add into one buffer must be ordered on a stream).
+ */
+typedef struct pww_probs_desc {
+    uint32_t size;            /* sizeof(pww_probs_desc_t) */
+    int32_t  images;          /* record images b < images (a CFG-folded batch is [cond rows; uncond rows]); 0 = all B */
+    int32_t  accumulate;      /* 0: out = weight * P      1: out += weight * P */
+    float    weight;
+    int64_t  out_stride[2];   /* image, row, in fp32 elements; row stride >= M, a multiple of 4 */
+} pww_probs_desc_t;
+
+int pww_cross_attn_probs(const void *q, const void *k, const float *bias,
+                         const double *stats, int32_t stat_kind, double stat_count, float coeff_scalar,
+                         const float *gate, const pww_attn_desc_t *desc, const pww_cross_opts_t *opts,
+                         float *out, const pww_probs_desc_t *pdesc, void *stream);
 
 /*
  * Per-image global statistics of the raw score tensor S = Q K^T over all heads, rows and keys

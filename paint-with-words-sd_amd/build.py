@@ -23,7 +23,7 @@ LIB = os.path.join(HERE, "pww_hip", "libpww_hip.so")
 LIB_EXPERIMENTS = os.path.join(HERE, "pww_hip", "libpww_hip_experiments.so")
 # (source, extra defines, object suffix): the instantiation units are compiled once per slice
 UNITS = [("pww_api.hip", [], ""), ("pww_attn.hip", [], ""), ("pww_cross.hip", [], ""), ("pww_cross_lean.hip", [], ""), ("pww_reduce.hip", [], ""),
-         ("pww_mask.hip", [], ""), ("pww_qproj.hip", [], ""), ("pww_norm.hip", [], ""), ("pww_blocks.hip", [], ""), ("pww_conv.hip", [], ""),
+         ("pww_mask.hip", [], ""), ("pww_qproj.hip", [], ""), ("pww_norm.hip", [], ""), ("pww_blocks.hip", [], ""), ("pww_conv.hip", [], ""), ("pww_probs.hip", [], ""),
          ("pww_attn_inst.hip", ["-DPWW_INST_F16"], ".f16"), ("pww_attn_inst.hip", ["-DPWW_INST_BF16"], ".bf16"),
          ("pww_cross_inst.hip", ["-DPWW_INST_F16", "-DPWW_INST_NW=2"], ".f16.nw2"), ("pww_cross_inst.hip", ["-DPWW_INST_F16", "-DPWW_INST_NW=4"], ".f16.nw4"),
          ("pww_cross_inst.hip", ["-DPWW_INST_BF16", "-DPWW_INST_NW=2"], ".bf16.nw2"), ("pww_cross_inst.hip", ["-DPWW_INST_BF16", "-DPWW_INST_NW=4"], ".bf16.nw4")]

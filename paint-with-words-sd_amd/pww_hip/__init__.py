@@ -5,6 +5,7 @@ from ._lib import PwwHipError, load as load_library, device_arch, LIB_PATH, EXPO
 from . import ops
 from . import blocks
 from .attention import QKProxy, ScaledW, inj_forward, install, uninstall, PwWAttnProcessor, pww_attention
+from .attnmaps import record_attention_maps, AttentionMaps
 
 
 
@@ -44,4 +45,4 @@ class miopen_find:
 
 
 __all__ = ["PwwHipError", "enable_miopen_find", "miopen_find", "load_library", "device_arch", "ops", "QKProxy", "ScaledW", "inj_forward", "install", "uninstall",
-           "PwWAttnProcessor", "pww_attention", "LIB_PATH", "EXPORTS"]
+           "PwWAttnProcessor", "pww_attention", "LIB_PATH", "EXPORTS", "record_attention_maps", "AttentionMaps"]

@@ -26,7 +26,7 @@ EXPORTS = ("pww_version", "pww_has_experiments", "pww_last_error", "pww_device_a
            "pww_workspace_bytes", "pww_profile_arm", "pww_profile_elapsed_us", "pww_profile_reset", "pww_debug_timeline", "pww_debug_path_counts",
            "pww_qproj_stat", "pww_qproj_parts", "pww_cross_attn_fwd_parts", "pww_mask_build_f32_levels", "pww_qk_parts", "pww_qk_parts_count",
            "pww_group_norm_fwd", "pww_group_norm_workspace_bytes", "pww_add_layer_norm", "pww_add_layer_norm_bias", "pww_geglu", "pww_bias_residual",
-           "pww_conv3x3_workspace_bytes", "pww_conv3x3_fwd")
+           "pww_conv3x3_workspace_bytes", "pww_conv3x3_fwd", "pww_cross_attn_probs")
 # ... and what only libpww_hip_experiments.so has on top of them (the header's "experiments" section)
 EXPERIMENT_EXPORTS = ("pww_cross_attn_fwd_fused", "pww_cross_attn_fwd_fused_ex", "pww_cross_fused_workspace_bytes", "pww_cross_fused_state_bytes",
                       "pww_cross_attn_fwd_parts_out", "pww_cross_attn_out_supported")
@@ -72,6 +72,12 @@ class ConvDesc(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("Hin", ctypes.c_int32), ("Win", ctypes.c_int32),
                 ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32), ("stride", ctypes.c_int32), ("upsample", ctypes.c_int32), ("tile_n", ctypes.c_int32),
                 ("splitk", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class ProbsDesc(ctypes.Structure):
+    """struct pww_probs_desc (head-averaged cross-attention probabilities; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("images", ctypes.c_int32), ("accumulate", ctypes.c_int32), ("weight", ctypes.c_float),
+                ("out_stride", ctypes.c_int64 * 2)]
 
 
 class Region(ctypes.Structure):
@@ -130,6 +136,9 @@ def _bind(lib, experiments):
     lib.pww_conv3x3_workspace_bytes.restype = ctypes.c_size_t
     lib.pww_conv3x3_fwd.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(ConvDesc), vp, ctypes.c_size_t, vp]
     lib.pww_conv3x3_fwd.restype = ctypes.c_int
+    lib.pww_cross_attn_probs.argtypes = [vp, vp, vp, vp, i32, ctypes.c_double, f32, vp, ctypes.POINTER(AttnDesc), ctypes.POINTER(CrossOpts), vp,
+                                         ctypes.POINTER(ProbsDesc), vp]
+    lib.pww_cross_attn_probs.restype = ctypes.c_int
     lib.pww_debug_timeline.argtypes = [vp, ctypes.c_size_t]
     lib.pww_debug_timeline.restype = None
     lib.pww_debug_path_counts.argtypes = [vp]

@@ -29,6 +29,7 @@ BIAS_COLS = "_PWW_BIAS_COLS"       # private context key: int, columns >= this o
 COMPACT_W = "_PWW_COMPACT_W_"      # private context key prefix: compact form [N, R] (or [B, N, R]) of CROSS_ATTENTION_WEIGHT_<N>
 COMPACT_IDX = "_PWW_COMPACT_IDX"   # private context key: int32 [R] (or [B, R]) columns of the compact slots, -1 = unused
 GATED_ROWS = "_PWW_GATED_ROWS"     # private context key: int, _PWW_ROW_GATE is 1 for exactly the first so many rows, 0 after (a CFG-folded batch)
+ATTN_RECORDER = "_PWW_ATTN_RECORDER"   # private context key of CONDITIONAL dicts: attnmaps.AttentionRecorder (pww_hip.record_attention_maps); absent = nothing is recorded
 # Where the score statistic of `weight_function(w, sigma, qk)` is formed (round 5): ALWAYS outside the attention launch -- as partials
 # that the attention launch folds at entry (pww_cross_attn_fwd_parts: nothing waits for another workgroup, nothing has to be resident,
 # no time-out path) -- either in the epilogue of the to_q GEMM (pww_qproj_stat, where qproj_route says it wins) or by one small launch
@@ -667,6 +668,7 @@ def _attention(attn, hidden_states, context, out_linear):
     compact = None
     gated = 0
     slots = context.get(COEFF_SLOTS) if (context is not None and is_dict) else None
+    rec = context.get(ATTN_RECORDER) if (context is not None and is_dict) else None
     if isinstance(bias, LazyStat):     # a bare statistic: a per-image constant on every logit of a row cancels in softmax
         bias = None
     sym = _symbolic_scalar(bias)
@@ -742,15 +744,54 @@ def _attention(attn, hidden_states, context, out_linear):
     elif slots is not None and stat is None:
         slots.unsupported = True       # a materialised bias tensor depends on sigma through torch ops
     if bias is None:
-        return ops.attention(query, key, value, attn.heads, attn.scale), False
+        out = ops.attention(query, key, value, attn.heads, attn.scale)
+        if rec is not None:
+            _record_probs(rec, attn, context, query, key, None, None, None, None)
+        return out, False
     if (out_linear is not None and stat is not None and stat[0] is None and scratch is None and key.shape[1] <= ops.FUSED_MAX_KEYS
             and out_linear.weight.dtype == query.dtype and ops.attention_out_supported(query, key, attn.heads, bias, out_linear.weight, bias_cols)):
         # row f-1 (opt-in, FUSE_TO_OUT): attention + to_out[0] in one launch; the dense map serves (the compact form is the general kernel's)
         wb = out_linear.bias
+        if rec is not None:
+            _warn_once("record_to_out", "attention maps: the attention + to_out launch of the experiments library is not recorded")
         return ops.attention_out(query, key, value, attn.heads, attn.scale, bias, out_linear.weight, wb if wb is None else wb.to(query.dtype),
                                  bias_coeff=gate, stat=stat, parts=parts, coeff_dev=coeff_dev, bias_cols=bias_cols, gated=gated), True
-    return ops.attention(query, key, value, attn.heads, attn.scale, bias=bias, bias_coeff=gate, stat=stat, scratch=scratch,
-                         coeff_dev=coeff_dev, bias_cols=bias_cols, compact=compact, gated=gated, parts=parts), False
+    if rec is None:
+        return ops.attention(query, key, value, attn.heads, attn.scale, bias=bias, bias_coeff=gate, stat=stat, scratch=scratch,
+                             coeff_dev=coeff_dev, bias_cols=bias_cols, compact=compact, gated=gated, parts=parts), False
+    # recording (pww_hip.record_attention_maps): the same launch, then one probabilities launch with the same q / k / map / coefficient
+    # inputs. The "parts" route folds its statistic inside the attention launch: that launch is asked to hand the folded fields out.
+    route = ops._attention_route(True, stat, scratch, parts, key.shape[1])
+    stats_out = None
+    if route == "parts" and stat[1] != ops.STAT_NONE and not rec.muted:
+        stats_out = torch.empty((query.shape[0], 4), dtype=torch.float64, device=query.device)
+    out = ops.attention(query, key, value, attn.heads, attn.scale, bias=bias, bias_coeff=gate, stat=stat, scratch=scratch, stats_out=stats_out,
+                        coeff_dev=coeff_dev, bias_cols=bias_cols, compact=compact, gated=gated, parts=parts)
+    if route == "fused":
+        _warn_once("record_fused", "attention maps: the in-launch statistic route of the experiments library (PWW_FUSED_CROSS=1) is not recorded")
+    elif route == "parts":
+        _record_probs(rec, attn, context, query, key, bias, gate, (stats_out, stat[1], stat[2]), coeff_dev)
+    else:       # "plain": c[b] = gate[b]; "stat": the [B, 4] statistics came with the call
+        _record_probs(rec, attn, context, query, key, bias, gate, stat, coeff_dev)
+    return out, False
+
+
+def _record_probs(rec, attn, context, query, key, bias, coeff, stat, coeff_dev):
+    """One ops.attention_probs launch behind the attention launch of a recorded cross-attention call: the head-averaged probabilities of the
+    conditional rows, added into the recorder's accumulator for this token count (or layer)."""
+    B, N, M = query.shape[0], query.shape[1], key.shape[1]
+    if M > ops.FUSED_MAX_KEYS:
+        _warn_once("record_keys", "attention maps: cross-attention over %d > %d keys is not recorded" % (M, ops.FUSED_MAX_KEYS))
+        return
+    gated = int(context.get(GATED_ROWS, 0) or 0) if context.get(ROW_GATE) is not None else 0
+    tgt = rec.target(attn, B, N, M, gated, query.device)
+    if tgt is None:
+        return
+    buf, images = tgt
+    if stat is not None and stat[0] is None and stat[1] != ops.STAT_NONE:
+        raise PwwHipError("attention maps: the attention launch's statistics are missing for this call")
+    ops.attention_probs(query, key, attn.heads, attn.scale, bias=bias, bias_coeff=coeff, stat=stat, coeff_dev=coeff_dev,
+                        images=images if images < B else 0, out=buf, accumulate=True)
 
 
 def inj_forward(self, hidden_states, context=None, mask=None):

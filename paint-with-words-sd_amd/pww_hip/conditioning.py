@@ -192,6 +192,9 @@ def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, 
         height, width = rgb.shape[:2]
         table = _parse_regions(color_context, tokenizer)
     token_lis = text_input["input_ids"][0].tolist()
+    from . import attnmaps
+    if attnmaps.active() is not None:       # (pww_hip.record_attention_maps: phrase lookup in the recorded maps needs the prompt's tokens)
+        attnmaps.active().note_prompt(tokenizer, token_lis)
     keys = [always_round(height / r) * always_round(width / r) for r in (8, 16, 32, 64)]
     if table:
         _warn_missing_colors(rgb, table)

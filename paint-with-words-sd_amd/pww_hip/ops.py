@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, CrossOpts, QprojDesc, Region, PwwHipError
+from ._lib import AttnDesc, CrossOpts, ProbsDesc, QprojDesc, Region, PwwHipError
 
 _DT = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 
@@ -347,6 +347,58 @@ def attention(q, k, v, heads, scale, bias=None, bias_coeff=None, stat=None, scra
             _launch_parts(lib, io, bias, bias_coeff, d, stat, parts, stats_out, coeff_dev, bias_cols, compact, gated)
         else:
             _launch_fused(io, bias, bias_coeff, d, stat, scratch, q.device, stats_out, coeff_dev, bias_cols, compact, gated)
+    return out
+
+
+def probs_buffer(images, N, M, device, zero=True):
+    """An fp32 [images, N, M] tensor attention_probs can write to: rows of M floats in storage padded to a multiple of 4 (16-byte aligned rows)."""
+    make = torch.zeros if zero else torch.empty
+    return make((images, N, (M + 3) & ~3), dtype=torch.float32, device=device)[:, :, :M]
+
+
+def attention_probs(q, k, heads, scale, bias=None, bias_coeff=None, stat=None, coeff_dev=None, images=0, out=None, accumulate=False, weight=1.0):
+    """weight * mean over heads of softmax((Q K^T + c * bias) * scale): the fp32 [images, N, M] probabilities the attention launch of the same
+    arguments keeps in registers (reference: `attention_scores.softmax(dim=-1)`, paint_with_words.py:112-114), from a launch of its own
+    (pww_cross_attn_probs, M <= 128). q, k, bias, bias_coeff and coeff_dev mean what they mean in `attention`; stat = (stats, kind, scalar) with
+    `stats` the float64 [B, 4] tensor of qk_stats -- or the `stats_out` a parts-route attention launch wrote -- and None only with STAT_NONE:
+    c[b] = scalar * stat(stats[b]) * bias_coeff[b]. Without `stat`: c[b] = bias_coeff[b]. images: only the first so many images are computed
+    (0 = all; a CFG-folded batch is [cond rows; uncond rows]). out: an fp32 [>= images, N, >= M] tensor to write to (unit stride along the keys, row
+    and image strides multiples of 4) -- with accumulate, to add to; returned as given."""
+    _require_gpu(q, k, bias, bias_coeff, out)
+    if q.dtype != k.dtype:
+        raise PwwHipError("q/k dtypes differ: %s %s" % (q.dtype, k.dtype))
+    q, k = _prep(q), _prep(k)
+    d = _desc(q, k, None, None, heads, scale)
+    B, N, M = d.B, d.N, d.M
+    if M > FUSED_MAX_KEYS:
+        raise PwwHipError("attention_probs takes at most %d keys (got %d)" % (FUSED_MAX_KEYS, M))
+    n_img = int(images or 0)
+    if n_img < 0 or n_img > B:
+        raise PwwHipError("attention_probs: images = %d outside 0 .. B = %d" % (n_img, B))
+    rows = n_img or B
+    if bias is not None:
+        bias = _bias_view(bias, d)
+        bias_coeff = _per_image_f32(bias_coeff, B, "bias_coeff", expand=True)
+    else:
+        bias_coeff = None
+    stats, kind, scalar = stat if stat is not None else (None, STAT_NONE, 1.0)
+    _check_f64(stats, "stat: stats", B, 4)
+    if stats is None and kind != STAT_NONE:
+        raise PwwHipError("attention_probs: a statistic needs its [B, 4] statistics (qk_stats, or the stats_out of the attention launch)")
+    if out is None:
+        if accumulate:
+            raise PwwHipError("attention_probs: accumulate needs `out`")
+        out = probs_buffer(rows, N, M, q.device, zero=False)
+    elif (out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] < rows or out.shape[1] != N or out.shape[2] < M or out.stride(2) != 1
+          or out.stride(1) % 4 or out.stride(0) % 4 or out.data_ptr() % 16 or out.device != q.device):
+        raise PwwHipError("attention_probs: `out` must be an fp32 [>= %d, %d, >= %d] tensor on %s, 16-byte aligned, unit key stride, row / image strides "
+                          "multiples of 4" % (rows, N, M, q.device))
+    pd = ProbsDesc(ctypes.sizeof(ProbsDesc), n_img, int(bool(accumulate)), float(weight))
+    pd.out_stride[:] = [out.stride(0), out.stride(1)]
+    op = _cross_opts(B, N, coeff_dev, 0, None)
+    with torch.cuda.device(q.device):
+        _lib.check(_lib.load().pww_cross_attn_probs(_ptr(q), _ptr(k), _ptr(bias), _ptr(stats), int(kind), float(d.H * N * M), float(scalar), _ptr(bias_coeff),
+                                                    ctypes.byref(d), _opt_ref(op), _ptr(out), ctypes.byref(pd), _stream()), "pww_cross_attn_probs")
     return out
 
 

@@ -18,7 +18,8 @@ Three execution modes over the SAME arithmetic:
 import torch
 
 from . import ops
-from .attention import install, refresh_kv_cache, refresh_orig_cache, ROW_GATE, KV_CACHE, COEFF_SLOTS, CoeffSlots, COMPACT_W, COMPACT_IDX, GATED_ROWS
+from . import attnmaps
+from .attention import install, refresh_kv_cache, refresh_orig_cache, ROW_GATE, KV_CACHE, COEFF_SLOTS, CoeffSlots, COMPACT_W, COMPACT_IDX, GATED_ROWS, ATTN_RECORDER
 from .conditioning import PwWContext
 
 ORIG = "CROSS_ATTENTION_WEIGHT_ORIG"
@@ -200,6 +201,7 @@ class _GraphedUNet:
         slots = context.get(COEFF_SLOTS)
         key = "all" if slots is not None and not slots.unsupported else step
         entry = self.graphs.get(key)
+        rec = context.get(ATTN_RECORDER)      # attention-map recording: its launches are ordinary nodes of the graph, behind each attention launch
         if entry is None:
             # warm-up on a side stream (required before capture; also the discovery pass of the coefficient slots), then capture
             if slots is not None:
@@ -207,8 +209,14 @@ class _GraphedUNet:
                 slots.begin_forward()
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self.unet(self.static_in, self.static_t, encoder_hidden_states=context)
+            if rec is not None:
+                rec.muted = True              # the warm-up pass only allocates the accumulators: what it computes is replayed right below
+            try:
+                with torch.cuda.stream(s):
+                    self.unet(self.static_in, self.static_t, encoder_hidden_states=context)
+            finally:
+                if rec is not None:
+                    rec.muted = False
             torch.cuda.current_stream().wait_stream(s)
             if slots is not None:
                 slots.discover = False
@@ -217,13 +225,20 @@ class _GraphedUNet:
             g = torch.cuda.CUDAGraph()
             if self.pool is None:
                 self.pool = torch.cuda.graph_pool_handle()
-            with torch.cuda.graph(g, pool=self.pool):
-                out = self.unet(self.static_in, self.static_t, encoder_hidden_states=context).sample
-            entry = (g, out)
+            if rec is not None:
+                rec.begin_trace()
+            try:
+                with torch.cuda.graph(g, pool=self.pool):
+                    out = self.unet(self.static_in, self.static_t, encoder_hidden_states=context).sample
+            finally:
+                trace = rec.end_trace() if rec is not None else None
+            entry = (g, out, trace)
             self.graphs[key] = entry
             self.captures += 1
-        g, out = entry
+        g, out, trace = entry
         g.replay()
+        if rec is not None and trace:
+            rec.replayed(trace)       # the host's tally of what the replay added to each accumulator
         return out
 
 
@@ -239,24 +254,28 @@ class PwWSampler:
         self._graph_sig = None
         self._fallback_sig = None
         self._static_folded = None
+        self._static_maps = {"bufs": {}, "meta": {}}           # hipGraph mode: the attention-map accumulators the captured probabilities launches add into
         self._request_folded = None
         self._scratch_modules = None
         self._errors = ops.FusedErrorWatch()
         self.handoff_pending = False     # the last request issued launches with an in-kernel hand-off (PWW_QPROJ_STAT=0 / shapes the
                                          # to_q GEMM does not cover): its latents must not reach a caller before check_errors() has looked
 
-    def _static_context(self, folded, weight_function, latents, timesteps):
+    def _static_context(self, folded, weight_function, latents, timesteps, rec=None):
         """Captured graphs read the context tensors by ADDRESS: keep one set of static tensors alive and copy each new
         request's values into them; rebuild the graphs when the geometry changes. The weight function and the schedule are
         NOT part of the key while the function's scalars travel in device words (CoeffSlots) -- fresh lambdas, other
         constants, another step count all replay the same graph; only the per-step fall-back keys them."""
         def tensor_sig(d):      # (the full-resolution fallback map is not part of the geometry: it exists only once a layer asked for it)
             return tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in d.items() if torch.is_tensor(v) and k != ORIG))
-        sig = (tuple(latents.shape), tensor_sig(folded), tuple(sorted((k, v) for k, v in folded.items() if isinstance(v, int) and not isinstance(v, bool))))
+        # (recording attention maps on / off, per layer or not, is geometry too: the captured graph holds the probabilities launches or it does not)
+        sig = (tuple(latents.shape), tensor_sig(folded), tuple(sorted((k, v) for k, v in folded.items() if isinstance(v, int) and not isinstance(v, bool))),
+               None if rec is None else ("attention maps", rec.per_layer))
         self._request_folded = folded
         if sig != self._graph_sig:
             self._graphed.reset()
             self._graph_sig = sig
+            self._static_maps = {"bufs": {}, "meta": {}}
             self._fallback_sig = None
             self._static_folded = PwWContext({k: (v.clone() if torch.is_tensor(v) else v) for k, v in folded.items() if k != ORIG})
             # CROSS_ATTENTION_WEIGHT_ORIG stays pending in the static context too: the first layer that takes the fallback (in the
@@ -271,6 +290,10 @@ class PwWSampler:
                 self._static_folded[ORIG].copy_(folded[ORIG])      # (builds this request's map: the captured layers read it)
             refresh_kv_cache(self._static_folded)     # new prompt embedding -> new K|V, same addresses
             refresh_orig_cache(self._static_folded)   # new color map -> new fallback maps, same addresses
+        if rec is not None:
+            self._static_folded[ATTN_RECORDER] = rec
+        else:
+            self._static_folded.pop(ATTN_RECORDER, None)
         slots = self._static_folded[COEFF_SLOTS]
         if slots.unsupported:      # one graph per step: those do depend on the function's constants and on the schedule
             fsig = (weight_function_signature(weight_function), tuple(float(t) for t in timesteps))
@@ -304,12 +327,31 @@ class PwWSampler:
             for d in conds + unconds:
                 d.setdefault(KV_CACHE, {}).clear()
         folded = None
+        rec = attnmaps.active()        # pww_hip.record_attention_maps(): the recorder rides in the conditional context(s) of this request
         if self.mode != "eager":
             folded = _fold_context(cond, uncond, n, dev)
             if self._graphed is not None:
-                folded = self._static_context(folded, weight_function, latents, timesteps)
+                folded = self._static_context(folded, weight_function, latents, timesteps, rec)
         if extra_channels is not None and extra_channels.shape[0] != n:
             extra_channels = extra_channels.expand(n, -1, -1, -1)
+        if rec is None:
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, None)
+        static = self._static_maps if self._graphed is not None else None
+        rec.begin_request(n, latents.shape[-2:], static=static)      # (hipGraph mode: zeroes the static accumulators, before the first replay)
+        holders = conds if folded is None else [folded]
+        for d in holders:
+            d[ATTN_RECORDER] = rec
+        try:
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec)
+        finally:
+            for d in holders:
+                d.pop(ATTN_RECORDER, None)
+            rec.end_request(static=static is not None)
+
+    def _denoise(self, conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec):
+        """The loop of sample() (reference :470-506)."""
+        sch, unet, n = self.scheduler, self.unet, latents.shape[0]
+        udt = unet.dtype if hasattr(unet, "dtype") else next(unet.parameters()).dtype
         for i, t in enumerate(timesteps):
             sigma, _ = self._sigma_and_index(i, t)
             x = sch.scale_model_input(latents, t)
@@ -319,6 +361,8 @@ class PwWSampler:
                 eps_c, eps_u = [], []
                 for j in range(n):   # the reference is batch-1 (:445); images are independent
                     conds[j].update({"SIGMA": sigma, "WEIGHT_FUNCTION": weight_function})
+                    if rec is not None:
+                        rec.row = j
                     eps_c.append(unet(x[j:j + 1], t, encoder_hidden_states=conds[j]).sample)
                     unconds[j].update({"SIGMA": sigma, "WEIGHT_FUNCTION": lambda w, sigma, qk: 0.0})
                     eps_u.append(unet(x[j:j + 1], t, encoder_hidden_states=unconds[j]).sample)
