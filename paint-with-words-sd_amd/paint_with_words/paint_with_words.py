@@ -20,6 +20,7 @@ from PIL import Image
 
 import pww_hip
 from pww_hip.attention import inj_forward  # noqa: F401  (same import path as the reference's symbol)
+from pww_hip.conditioning import check_prompt_chunks, prompt_chunk_count
 from pww_hip.conditioning import (always_round, _extract_seed_and_sigma_from_context, _encode_text_color_inputs,  # noqa: F401
                                   _get_binary_mask, gaussian_blur_mask)
 from pww_hip.sampler import PwWSampler, initial_latents
@@ -102,9 +103,16 @@ def _broadcast(value, n, name):
     return [value] * n, True
 
 
+def _batch_prompt_chunks(tokenizer, prompts, max_prompt_chunks):
+    """Chunks every image of a call is encoded to: the largest count any of its prompts needs under the cap (1 with the default cap)."""
+    if check_prompt_chunks(max_prompt_chunks) == 1:
+        return 1
+    return max(prompt_chunk_count(tokenizer, p, max_prompt_chunks) for p in prompts)
+
+
 def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale,
               weight_function, unconditional_input_prompt, init_images=None, strength=0.5, latent_hw=None,
-              on_step=None, use_region_sigma=True, shared=False):
+              on_step=None, use_region_sigma=True, shared=False, max_prompt_chunks=1):
     """Shared body of paint_with_words / paint_with_words_batch / the pipeline class (reference :414-506): conditioning
     per request (once if every request shares map, context and prompt), CPU-generated latents per seed exactly as :446,
     one denoise loop over all images. Returns the final latents [n, 4, h, w]."""
@@ -112,10 +120,11 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
     n = len(seeds)
     sampler = _sampler_for(unet, scheduler, DEFAULT_MODE)   # also installs the attention plug
     conds, unconds, seeds_info = [], [], []
+    min_chunks = _batch_prompt_chunks(tokenizer, prompts[:1] if shared else prompts, max_prompt_chunks)
     for i in range(1 if shared else n):
         extra_seeds, region_info, cond, uncond = _encode_text_color_inputs(
             text_encoder, tokenizer, device, color_map_images[i], color_contexts[i], prompts[i], unconditional_input_prompt,
-            dtype=_unet_dtype(unet), use_sigma=use_region_sigma)
+            dtype=_unet_dtype(unet), use_sigma=use_region_sigma, max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks)
         conds.append(cond), unconds.append(uncond), seeds_info.append((extra_seeds, region_info))
     if shared:
         conds, unconds, seeds_info = conds[0], unconds[0], seeds_info * n
@@ -167,15 +176,20 @@ def paint_with_words(
     init_image: Optional[Image.Image] = None,
     strength: float = 0.5,
     return_latents: bool = False,
+    max_prompt_chunks: int = 1,
 ):
     """reference :391-510. `return_latents=True` (extension) returns the final latent tensor instead
-    of decoding it -- the quantity parity is checked on."""
+    of decoding it -- the quantity parity is checked on. `max_prompt_chunks` (extension; 1, 2 or 3): a prompt longer than 75 tokens is
+    encoded in up to that many 75-token chunks (154 / 231 keys) instead of cut at 77; with the default every request is tokenized as in
+    the reference, and a prompt that needs fewer chunks than the cap gets only the chunks it needs."""
+    check_prompt_chunks(max_prompt_chunks)
     color_map_image.size     # the reference dereferences it unconditionally (:414): None raises here too
     tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
                             model_token=model_token) if preloaded_utils is None else preloaded_utils)
     latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps,
                         guidance_scale, weight_function, unconditional_input_prompt,
-                        init_images=None if init_image is None else [init_image], strength=strength, shared=True)
+                        init_images=None if init_image is None else [init_image], strength=strength, shared=True,
+                        max_prompt_chunks=max_prompt_chunks)
     if return_latents:
         return _sampler_for(tools[1], tools[4], DEFAULT_MODE).checked(latents)
     image = _pil_from_latents(tools[0], latents)[0]
@@ -202,6 +216,7 @@ def paint_with_words_batch(
     init_images: Union[None, Image.Image, Sequence[Image.Image]] = None,
     strength: float = 0.5,
     return_latents: bool = False,
+    max_prompt_chunks: int = 1,
 ):
     """len(seeds) requests through ONE denoise loop (the reference's multi-sample path is a
     sequential loop of paint_with_words calls, gradio_pww.py:24-45). `color_contexts`, `color_map_images`,
@@ -210,7 +225,9 @@ def paint_with_words_batch(
     statistic and region seeds, so image i equals `paint_with_words(color_contexts[i], color_map_images[i],
     input_prompts[i], seed=seeds[i], ...)`. All color maps of one call must have the same size. The caller's
     color_context dicts are mutated like the single-image call mutates its dict (:296). Returns a list of PIL images
-    (or the [n, 4, h, w] latents with return_latents=True)."""
+    (or the [n, 4, h, w] latents with return_latents=True). max_prompt_chunks: see paint_with_words; with per-image prompts every image
+    is padded (with empty chunks) to the largest chunk count of the batch."""
+    check_prompt_chunks(max_prompt_chunks)
     seeds = list(seeds)
     n = len(seeds)
     if n == 0:
@@ -229,7 +246,7 @@ def paint_with_words_batch(
     tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
                             model_token=model_token) if preloaded_utils is None else preloaded_utils)
     latents = _generate(tools, device, ctxs, maps, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
-                        unconditional_input_prompt, init_images=inits, strength=strength, shared=shared)
+                        unconditional_input_prompt, init_images=inits, strength=strength, shared=shared, max_prompt_chunks=max_prompt_chunks)
     if not shared:
         for c in {id(c): c for c in originals}.values():
             _extract_seed_and_sigma_from_context(c)

@@ -14,7 +14,8 @@ import pww_hip
 from pww_hip import ops
 _pw_module_name = __name__.rsplit(".", 1)[0] + ".paint_with_words"      # the function-API module: its DEFAULT_MODE is read at call time
 from .paint_with_words import (LMSDiscreteScheduler, pww_load_tools, preprocess, _pil_from_latents,
-                               _encode_text_color_inputs, _sampler_for, _unet_dtype, _broadcast)
+                               _encode_text_color_inputs, _sampler_for, _unet_dtype, _broadcast, _batch_prompt_chunks,
+                               check_prompt_chunks)
 
 
 def _mode():
@@ -115,20 +116,22 @@ def _inpaint_inputs(vae, init_image, mask_image, seed, scheduler, timesteps, dev
 
 def _generate_inpaint(tools, device, color_contexts, color_map_images, mask_images, init_images, prompts, seeds,
                       num_inference_steps, guidance_scale, weight_function, unconditional_input_prompt, strength, shared,
-                      on_step=None, mask_hw=None, resize_inputs=True, use_region_sigma=True):
+                      on_step=None, mask_hw=None, resize_inputs=True, use_region_sigma=True, max_prompt_chunks=1):
     """Shared body of paint_with_words_inpaint / _batch / the inpaint pipeline class. The function API resizes color map and
     mask to the init image (:172-173, `resize_inputs`); the pipeline class does not and sizes the latent mask by `mask_hw`."""
     vae, unet, text_encoder, tokenizer, scheduler = tools
     n = len(seeds)
     sampler = _sampler_for(unet, scheduler, _mode())
     conds, unconds = [], []
+    min_chunks = _batch_prompt_chunks(tokenizer, prompts[:1] if shared else prompts, max_prompt_chunks)
     for i in range(1 if shared else n):
         width, height = init_images[i].size
         color_map = color_map_images[i]
         if resize_inputs and color_map is not None:
             color_map = color_map.resize((width, height), Image.NEAREST)            # :172
         _, _, cond, uncond = _encode_text_color_inputs(text_encoder, tokenizer, device, color_map, color_contexts[i], prompts[i],
-                                                       unconditional_input_prompt, dtype=_unet_dtype(unet), use_sigma=use_region_sigma)
+                                                       unconditional_input_prompt, dtype=_unet_dtype(unet), use_sigma=use_region_sigma,
+                                                       max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks)
         conds.append(cond), unconds.append(uncond)
     if shared:
         conds, unconds = conds[0], unconds[0]
@@ -180,13 +183,15 @@ def paint_with_words_inpaint(
     model_token: Optional[str] = None,
     strength: float = 1.0,
     return_latents: bool = False,
+    max_prompt_chunks: int = 1,
 ):
-    """reference :137-270."""
+    """reference :137-270. max_prompt_chunks (extension): see paint_with_words."""
+    check_prompt_chunks(max_prompt_chunks)
     tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
                             model_token=model_token) if preloaded_utils is None else preloaded_utils)
     latents = _generate_inpaint(tools, device, [color_context], [color_map_image], [mask_image], [init_image], [input_prompt],
                                 [seed], num_inference_steps, guidance_scale, weight_function, unconditional_input_prompt,
-                                strength, shared=True)
+                                strength, shared=True, max_prompt_chunks=max_prompt_chunks)
     if return_latents:
         return _sampler_for(tools[1], tools[4], _mode()).checked(latents)
     image = _pil_from_latents(tools[0], latents)[0]
@@ -214,10 +219,12 @@ def paint_with_words_inpaint_batch(
     model_token: Optional[str] = None,
     strength: float = 1.0,
     return_latents: bool = False,
+    max_prompt_chunks: int = 1,
 ):
     """len(seeds) inpainting requests through one denoise loop (see paint_with_words_batch): each of the image-like
     arguments and the prompt is one shared value or a sequence with one entry per seed; all init images of a call must
-    have the same size. Image i equals the single-request call on request i."""
+    have the same size. Image i equals the single-request call on request i. max_prompt_chunks: see paint_with_words_batch."""
+    check_prompt_chunks(max_prompt_chunks)
     seeds = list(seeds)
     n = len(seeds)
     if n == 0:
@@ -234,7 +241,8 @@ def paint_with_words_inpaint_batch(
     tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
                             model_token=model_token) if preloaded_utils is None else preloaded_utils)
     latents = _generate_inpaint(tools, device, ctxs, maps, masks, inits, prompts, seeds, num_inference_steps, guidance_scale,
-                                weight_function, unconditional_input_prompt, strength, shared=s1 and s2 and s3)
+                                weight_function, unconditional_input_prompt, strength, shared=s1 and s2 and s3,
+                                max_prompt_chunks=max_prompt_chunks)
     if return_latents:
         return _sampler_for(tools[1], tools[4], _mode()).checked(latents)
     images = _pil_from_latents(tools[0], latents)

@@ -12,6 +12,9 @@ LIB_PATH = os.environ.get("PWW_HIP_LIB", os.path.join(_HERE, "libpww_hip.so"))
 # "experiments"). Tests and A/B tools load it (`load_experiments()`, or a whole process through PWW_HIP_LIB); the product never does.
 EXPERIMENTS_LIB_PATH = os.environ.get("PWW_HIP_EXPERIMENTS_LIB", os.path.join(_HERE, "libpww_hip_experiments.so"))
 
+# the launches of prompts longer than 77 tokens (128 < M <= 256 keys; include/pww_hip_long.h): loaded on the first long-prompt call (`load_long()`)
+LONG_LIB_PATH = os.environ.get("PWW_HIP_LONG_LIB", os.path.join(_HERE, "libpww_hip_long.so"))
+
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 126        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
 DTYPE_F16, DTYPE_BF16 = 0, 1
@@ -30,6 +33,13 @@ EXPORTS = ("pww_version", "pww_has_experiments", "pww_last_error", "pww_device_a
 # ... and what only libpww_hip_experiments.so has on top of them (the header's "experiments" section)
 EXPERIMENT_EXPORTS = ("pww_cross_attn_fwd_fused", "pww_cross_attn_fwd_fused_ex", "pww_cross_fused_workspace_bytes", "pww_cross_fused_state_bytes",
                       "pww_cross_attn_fwd_parts_out", "pww_cross_attn_out_supported")
+
+
+# every symbol include/pww_hip_long.h declares for libpww_hip_long.so
+LONG_EXPORTS = ("pww_long_version", "pww_long_last_error", "pww_long_qk_parts", "pww_long_qk_parts_count", "pww_long_cross_attn_fwd_parts",
+                "pww_long_cross_attn_probs", "pww_long_profile_arm", "pww_long_profile_elapsed_us")
+LONG_MIN_VERSION = 100
+LONG_MIN_KEYS, LONG_MAX_KEYS = 129, 256
 
 
 class AttnDesc(ctypes.Structure):
@@ -221,6 +231,43 @@ def load_experiments():
         raise PwwHipError("%s was not built with -DPWW_EXPERIMENTS=1" % EXPERIMENTS_LIB_PATH)
     _exp = _bind(lib, True)
     return _exp
+
+
+_long = None
+
+
+def load_long():
+    """libpww_hip_long.so (the cross-attention launches over 129 .. 256 keys), loaded once, on the first long-prompt call. A missing file raises:
+    there is no second implementation to fall back to."""
+    global _long
+    if _long is not None:
+        return _long
+    if not os.path.isfile(LONG_LIB_PATH):
+        raise PwwHipError("libpww_hip_long.so not found at %s: prompts longer than 77 tokens need it. Build it with "
+                          "`python paint-with-words-sd_amd/build.py` (or __graft_entry__.build())." % LONG_LIB_PATH)
+    lib = ctypes.CDLL(LONG_LIB_PATH)
+    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
+    lib.pww_long_version.restype = ctypes.c_int
+    if lib.pww_long_version() // 100 != 1 or lib.pww_long_version() < LONG_MIN_VERSION:
+        raise PwwHipError("libpww_hip_long ABI version %d is not 1.x >= %d (rebuild: python paint-with-words-sd_amd/build.py)"
+                          % (lib.pww_long_version(), LONG_MIN_VERSION))
+    lib.pww_long_last_error.restype = ctypes.c_char_p
+    lib.pww_last_error = lib.pww_long_last_error         # (`check(rc, what, lib)` asks the library it is given)
+    lib.pww_long_qk_parts.argtypes = [vp, vp, vp, ctypes.POINTER(AttnDesc), i32, i32, vp, ctypes.c_size_t, vp]
+    lib.pww_long_qk_parts.restype = ctypes.c_int
+    lib.pww_long_qk_parts_count.argtypes = [ctypes.POINTER(AttnDesc)]
+    lib.pww_long_qk_parts_count.restype = ctypes.c_int32
+    lib.pww_long_cross_attn_fwd_parts.argtypes = [vp, vp, vp, vp, vp, i32, f32, vp, ctypes.POINTER(AttnDesc), vp, i32, vp, ctypes.POINTER(CrossOpts), vp]
+    lib.pww_long_cross_attn_fwd_parts.restype = ctypes.c_int
+    lib.pww_long_cross_attn_probs.argtypes = [vp, vp, vp, vp, i32, ctypes.c_double, f32, vp, ctypes.POINTER(AttnDesc), ctypes.POINTER(CrossOpts), vp,
+                                              ctypes.POINTER(ProbsDesc), vp]
+    lib.pww_long_cross_attn_probs.restype = ctypes.c_int
+    lib.pww_long_profile_arm.argtypes = []
+    lib.pww_long_profile_arm.restype = ctypes.c_int
+    lib.pww_long_profile_elapsed_us.argtypes = [ctypes.POINTER(ctypes.c_float)]
+    lib.pww_long_profile_elapsed_us.restype = ctypes.c_int
+    _long = lib
+    return _long
 
 
 class experiments:

@@ -710,6 +710,14 @@ def _attention(attn, hidden_states, context, out_linear):
             if kind != ops.STAT_NONE:
                 parts = ops.qk_parts(query, key, attn.heads, kind, gate=gate, gated=gated)
             stat = (None, kind, scalar)
+        elif not have_stats and ops.long_keys(key.shape[1]):
+            # a prompt encoded in 2 or 3 chunks (154 / 231 keys): the same pair of launches from libpww_hip_long.so -- stock to_q on every
+            # layer, the statistic's partials over the finished Q, pass-2-only attention over four 64-key tiles
+            if query is None:
+                query = _half(lazy_q.get(), cdt)
+            if kind != ops.STAT_NONE:
+                parts = ops.long_qk_parts(query, key, attn.heads, kind, gate=gate, gated=gated)
+            stat = (None, kind, scalar)
         else:
             stat = (bias.stat.stats() if bias.stat is not None else None, kind, scalar)
         bias = w_map
@@ -762,6 +770,8 @@ def _attention(attn, hidden_states, context, out_linear):
     # recording (pww_hip.record_attention_maps): the same launch, then one probabilities launch with the same q / k / map / coefficient
     # inputs. The "parts" route folds its statistic inside the attention launch: that launch is asked to hand the folded fields out.
     route = ops._attention_route(True, stat, scratch, parts, key.shape[1])
+    if stat is not None and stat[0] is None and scratch is None and ops.long_keys(key.shape[1]):
+        route = "parts"     # (ops.attention's "long" route: the parts contract over 129 .. 256 keys)
     stats_out = None
     if route == "parts" and stat[1] != ops.STAT_NONE and not rec.muted:
         stats_out = torch.empty((query.shape[0], 4), dtype=torch.float64, device=query.device)
@@ -780,8 +790,8 @@ def _record_probs(rec, attn, context, query, key, bias, coeff, stat, coeff_dev):
     """One ops.attention_probs launch behind the attention launch of a recorded cross-attention call: the head-averaged probabilities of the
     conditional rows, added into the recorder's accumulator for this token count (or layer)."""
     B, N, M = query.shape[0], query.shape[1], key.shape[1]
-    if M > ops.FUSED_MAX_KEYS:
-        _warn_once("record_keys", "attention maps: cross-attention over %d > %d keys is not recorded" % (M, ops.FUSED_MAX_KEYS))
+    if M > ops.LONG_MAX_KEYS:
+        _warn_once("record_keys", "attention maps: cross-attention over %d > %d keys is not recorded" % (M, ops.LONG_MAX_KEYS))
         return
     gated = int(context.get(GATED_ROWS, 0) or 0) if context.get(ROW_GATE) is not None else 0
     tgt = rec.target(attn, B, N, M, gated, query.device)

@@ -48,6 +48,14 @@ def record_attention_maps(per_layer=False):
         _tls.recorder = None
 
 
+class _ChunkedPrompt(list):
+    """The framed ids of a prompt encoded in several chunks (a list, like a one-chunk prompt's entry) + its unframed content ids."""
+
+    def __init__(self, token_ids, content_ids, per):
+        super().__init__(token_ids)
+        self.content, self.per = list(content_ids), per
+
+
 class AttentionRecorder:
     """Host side of the recording mode: owns the accumulators, counts the contributions per accumulator (layers x UNet evaluations), and
     is what attention._attention finds under the ATTN_RECORDER key of a conditional context dict."""
@@ -100,9 +108,11 @@ class AttentionRecorder:
         for key, n in trace.items():
             self.counts[key] = self.counts.get(key, 0) + n
 
-    def note_prompt(self, tokenizer, token_ids):
+    def note_prompt(self, tokenizer, token_ids, content_ids=None):
+        """token_ids: the prompt's key columns (77 k framed ids). content_ids: with a prompt encoded in several chunks, its unframed ids --
+        phrases are matched on them and mapped to columns like the weight maps' (conditioning.framed_column)."""
         self.tokenizer = tokenizer
-        self.prompts.append(list(token_ids))
+        self.prompts.append(list(token_ids) if content_ids is None else _ChunkedPrompt(token_ids, content_ids, tokenizer.model_max_length - 2))
 
     # -- what the attention plug calls ------------------------------------------------------------
     def target(self, attn, B, N, M, gated, device):
@@ -213,7 +223,12 @@ class AttentionMaps:
         ids = list(self.tokenizer(text, max_length=self.tokenizer.model_max_length, truncation=True)["input_ids"][1:-1])
         toks = self.prompts[image if len(self.prompts) > 1 else 0]
         L = len(ids)
-        cols = sorted({c for i in range(len(toks)) if L and toks[i:i + L] == ids for c in range(i, i + L)})
+        if isinstance(toks, _ChunkedPrompt):
+            from .conditioning import framed_column
+            inner = toks.content
+            cols = sorted({framed_column(c, toks.per) for i in range(len(inner)) if L and inner[i:i + L] == ids for c in range(i, min(i + L, len(inner)))})
+        else:
+            cols = sorted({c for i in range(len(toks)) if L and toks[i:i + L] == ids for c in range(i, i + L)})
         if not cols:
             raise PwwHipError("phrase %r does not occur in the prompt" % (text,))
         return cols

@@ -104,6 +104,61 @@ def _parse_regions(color_context, tokenizer):
     return table
 
 
+MAX_PROMPT_CHUNKS = 3     # chunked prompt encoding: 77, 154 or 231 keys (libpww_hip_long.so serves 128 < M <= 256)
+
+
+def check_prompt_chunks(max_prompt_chunks):
+    """The `max_prompt_chunks` keyword of the entry points: an int in 1 .. MAX_PROMPT_CHUNKS."""
+    if isinstance(max_prompt_chunks, bool) or not isinstance(max_prompt_chunks, int) or not 1 <= max_prompt_chunks <= MAX_PROMPT_CHUNKS:
+        raise ValueError("max_prompt_chunks must be 1, 2 or %d (got %r): prompts of more than %d chunks are not supported"
+                         % (MAX_PROMPT_CHUNKS, max_prompt_chunks, MAX_PROMPT_CHUNKS))
+    return max_prompt_chunks
+
+
+def _content_ids(tokenizer, text):
+    """Token ids of `text` without truncation and without the BOS / EOS frame."""
+    return list(tokenizer(text, max_length=1 << 20, truncation=False)["input_ids"][1:-1])
+
+
+def prompt_chunk_count(tokenizer, prompt, max_prompt_chunks=1):
+    """Chunks of model_max_length - 2 content tokens `prompt` needs, at most `max_prompt_chunks` (an empty prompt needs one)."""
+    per = tokenizer.model_max_length - 2
+    return max(1, min(check_prompt_chunks(max_prompt_chunks), -(-len(_content_ids(tokenizer, prompt)) // per)))
+
+
+def chunk_prompt(tokenizer, prompt, max_prompt_chunks=1, min_chunks=1):
+    """Chunked prompt encoding, host half: -> (content ids, id rows [k][model_max_length]). The content ids (no BOS / EOS) are split into
+    chunks of model_max_length - 2; each chunk is framed BOS ... EOS and padded with EOS. k = the chunks the prompt needs, at least
+    `min_chunks` (a batch pads every image to its largest k with empty chunks), at most `max_prompt_chunks`: content past the cap is cut."""
+    L = tokenizer.model_max_length
+    per = L - 2
+    cap = check_prompt_chunks(max_prompt_chunks)
+    ids = _content_ids(tokenizer, prompt)
+    k = min(cap, max(1, min_chunks, -(-len(ids) // per)))
+    ids = ids[:k * per]
+    bos, eos = tokenizer("", max_length=L, truncation=True)["input_ids"][:2]
+    rows = []
+    for j in range(k):
+        piece = ids[j * per:(j + 1) * per]
+        rows.append([bos] + piece + [eos] * (L - 1 - len(piece)))
+    return ids, rows
+
+
+def framed_column(p, per=75):
+    """Column of content position `p` in the concatenated chunks: every chunk adds a BOS in front and an EOS behind its `per` tokens."""
+    return 1 + p + 2 * (p // per)
+
+
+def framed_column_lists(table, content_ids, n_chunks, per=75):
+    """_column_lists over the UNFRAMED content ids, scattered into the 77 k columns of the chunked prompt: a phrase that straddles a chunk
+    boundary keeps all its columns, and nothing depends on where the split falls."""
+    inner = _column_lists(table, content_ids)
+    cols = [[] for _ in range(n_chunks * (per + 2))]
+    for p, lst in enumerate(inner):
+        cols[framed_column(p, per)] = lst
+    return cols
+
+
 def _column_lists(table, token_lis, ratio_tag="8"):
     """For every prompt position the region ordinals accumulated into it, in the reference's order
     (:257-268); warns like :270-271 when a phrase does not occur in the prompt."""
@@ -127,13 +182,15 @@ def gaussian_blur_mask(mask, sigma, ksize=39):
     return ops.gauss_blur(mask, sigma, ksize)
 
 
-def build_weight_maps(color_map_rgb, table, token_lis, device, extra_sigmas=None, with_orig=False):
+def build_weight_maps(color_map_rgb, table, token_lis, device, extra_sigmas=None, with_orig=False, cols=None):
     """RGB map -> {N_8: [N, T], ...} fp32 device tensors, keyed like :370-377 -- ONE launch for the four resolutions -- plus
     "ORIG_THUNK": a callable that builds the [H, W, T] ratio-1 map on demand (with_orig=True: built now, key "ORIG").
-    color_map_rgb: uint8 numpy / tensor [H, W, 3]."""
+    color_map_rgb: uint8 numpy / tensor [H, W, 3]. cols: the column lists, if the caller matched the phrases itself (chunked prompts:
+    framed_column_lists); default: _column_lists over token_lis."""
     rgb = torch.as_tensor(np.ascontiguousarray(color_map_rgb), dtype=torch.uint8).to(device)
     H, W = rgb.shape[:2]
-    cols = _column_lists(table, token_lis)
+    if cols is None:
+        cols = _column_lists(table, token_lis)
     regions = [(c[0], c[1], c[2], s) for (_, c, s) in table]
     ratios = (8, 16, 32, 64)
     blurred = {}
@@ -172,12 +229,20 @@ def _warn_missing_colors(color_map_rgb, table):
 
 
 def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, color_context, input_prompt,
-                              unconditional_input_prompt, dtype=None, use_sigma=True):
+                              unconditional_input_prompt, dtype=None, use_sigma=True, max_prompt_chunks=1, min_prompt_chunks=1):
     """:315-388 with the weight maps built by the HIP mask kernel. Returns
     (extra_seeds, seperated_word_contexts, encoder_hidden_states, uncond_encoder_hidden_states);
     `seperated_word_contexts` is (region table [(token_ids, (r,g,b), strength)], rgb, {ordinal: blurred mask}) (the
     reference returns full-resolution float masks here; the only consumer, region seeding :451, gets what it
-    needs from the table + color map, plus the blurred masks of the regions that carry a sigma)."""
+    needs from the table + color map, plus the blurred masks of the regions that carry a sigma).
+    max_prompt_chunks > 1: a prompt of more than model_max_length - 2 tokens is encoded in up to that many chunks (chunk_prompt), each by
+    the text encoder on its own, concatenated along the token axis: CONTEXT_TENSOR [1, 77 k, ctx], weight maps [N, 77 k]. A prompt that needs
+    one chunk takes the code path of the default, whatever the cap. min_prompt_chunks: pad to that many chunks (per-image prompts of a batch)."""
+    chunk_rows = None
+    if check_prompt_chunks(max_prompt_chunks) > 1 or min_prompt_chunks > 1:
+        content_ids, rows = chunk_prompt(tokenizer, input_prompt, max_prompt_chunks, min_prompt_chunks)
+        if len(rows) > 1:
+            chunk_rows = rows
     text_input = tokenizer([input_prompt], padding="max_length", max_length=tokenizer.model_max_length,
                            truncation=True, return_tensors="pt")
     color_context, extra_seeds, extra_sigmas = _extract_seed_and_sigma_from_context(color_context)
@@ -191,14 +256,15 @@ def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, 
         rgb = np.array(color_map_image.convert("RGB")) if hasattr(color_map_image, "convert") else np.asarray(color_map_image)
         height, width = rgb.shape[:2]
         table = _parse_regions(color_context, tokenizer)
-    token_lis = text_input["input_ids"][0].tolist()
+    token_lis = text_input["input_ids"][0].tolist() if chunk_rows is None else [t for row in chunk_rows for t in row]
     from . import attnmaps
     if attnmaps.active() is not None:       # (pww_hip.record_attention_maps: phrase lookup in the recorded maps needs the prompt's tokens)
-        attnmaps.active().note_prompt(tokenizer, token_lis)
+        attnmaps.active().note_prompt(tokenizer, token_lis, None if chunk_rows is None else content_ids)
     keys = [always_round(height / r) * always_round(width / r) for r in (8, 16, 32, 64)]
     if table:
         _warn_missing_colors(rgb, table)
-        maps = build_weight_maps(rgb, table, token_lis, device, extra_sigmas)
+        cols = None if chunk_rows is None else framed_column_lists(table, content_ids, len(chunk_rows), tokenizer.model_max_length - 2)
+        maps = build_weight_maps(rgb, table, token_lis, device, extra_sigmas, cols=cols)
         blurred = maps.pop("_BLURRED")
         nz_cols = maps.pop("_COLS")
     else:   # empty color_context (:242-243): all-zero maps
@@ -207,10 +273,17 @@ def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, 
         blurred = {}
         nz_cols = None
 
-    cond_embeddings = text_encoder(text_input.input_ids.to(device))[0]
-    uncond_input = tokenizer([unconditional_input_prompt], padding="max_length",
-                             max_length=text_input.input_ids.shape[-1], return_tensors="pt")
-    uncond_embeddings = text_encoder(uncond_input.input_ids.to(device))[0]
+    if chunk_rows is None:
+        cond_embeddings = text_encoder(text_input.input_ids.to(device))[0]
+        uncond_input = tokenizer([unconditional_input_prompt], padding="max_length",
+                                 max_length=text_input.input_ids.shape[-1], return_tensors="pt")
+        uncond_embeddings = text_encoder(uncond_input.input_ids.to(device))[0]
+    else:
+        # every chunk through the text encoder on its own (it sees 77 positions, as it was trained), the unconditional prompt to the same k
+        k = len(chunk_rows)
+        _, uncond_rows = chunk_prompt(tokenizer, unconditional_input_prompt, k, k)
+        encode = lambda rows: torch.cat([text_encoder(torch.tensor([row], dtype=torch.long).to(device))[0] for row in rows], dim=1)  # noqa: E731
+        cond_embeddings, uncond_embeddings = encode(chunk_rows), encode(uncond_rows)
     if dtype is not None:
         cond_embeddings, uncond_embeddings = cond_embeddings.to(dtype), uncond_embeddings.to(dtype)
 

@@ -69,6 +69,7 @@ def _prep(t):
 
 STAT_NONE, STAT_MAX, STAT_MIN, STAT_MEAN, STAT_STD, STAT_ABSMAX, STAT_ALL = 0, 1, 2, 3, 4, 5, 6   # PWW_STAT_* of include/pww_hip.h
 FUSED_MAX_KEYS = 128   # pww_cross_attn_fwd_fused: one K/V stage
+LONG_MAX_KEYS = _lib.LONG_MAX_KEYS   # libpww_hip_long.so: the same pair of launches for FUSED_MAX_KEYS < M <= 256 (prompts encoded in 2 / 3 chunks)
 COMPACT_MAX_R = 32     # pww_cross.hip: the compact form holds at most 32 non-zero columns
 
 
@@ -294,6 +295,33 @@ def _launch_parts(lib, io, bias, coeff, d, stat, parts, stats_out, coeff_dev, bi
                "pww_cross_attn_fwd_parts")
 
 
+def long_keys(M):
+    """True for the key counts libpww_hip_long.so serves: prompts encoded in 2 or 3 chunks of 77 tokens (any FUSED_MAX_KEYS < M <= LONG_MAX_KEYS)."""
+    return FUSED_MAX_KEYS < M <= LONG_MAX_KEYS
+
+
+def _launch_long(io, bias, coeff, d, stat, parts, stats_out, coeff_dev, bias_cols, gated):
+    """_launch_parts for FUSED_MAX_KEYS < M <= LONG_MAX_KEYS: pww_long_cross_attn_fwd_parts (partials from long_qk_parts; none for STAT_NONE).
+    The compact form of the map is an experiments-library form of the <= 128-key kernel; ops.attention does not hand it on: here the dense
+    map, which every caller passes beside it, serves (as in _launch_parts on the product library)."""
+    _, kind, scalar = stat
+    if kind != STAT_NONE and parts is None:
+        raise PwwHipError("a statistic over %d keys needs its partials (long_qk_parts)" % d.M)
+    _check_f64(parts, "parts", d.B, "nparts", 4)
+    _check_f64(stats_out, "stats_out", d.B, 4)
+    op = _cross_opts(d.B, d.N, coeff_dev, bias_cols, None, gated)
+    lib = _lib.load_long()
+    # partials over more than FUSED_MAX_KEYS keys have one producer, and its count is a function of the problem: anything else (partials of
+    # qproj_stat / qk_parts, which stop at 128 keys; another layer's) does not describe this Q K^T
+    want = int(lib.pww_long_qk_parts_count(ctypes.byref(d))) if parts is not None else 0
+    if parts is not None and parts.shape[1] != want:
+        raise PwwHipError("cross-attention over %d keys folds the partials of long_qk_parts (%d per image for this problem), got %d: the pass-2-only "
+                          "launch of libpww_hip.so takes at most %d keys" % (d.M, want, parts.shape[1], FUSED_MAX_KEYS))
+    _lib.check(lib.pww_long_cross_attn_fwd_parts(*io, _ptr(bias), int(kind), float(scalar), _ptr(coeff), ctypes.byref(d), _ptr(parts),
+                                                 int(parts.shape[1]) if parts is not None else 0, _ptr(stats_out), _opt_ref(op), _stream()),
+               "pww_long_cross_attn_fwd_parts", lib)
+
+
 def _launch_fused(io, bias, coeff, d, stat, scratch, device, stats_out, coeff_dev, bias_cols, compact, gated):
     """The statistic formed in the attention launch itself, through the workgroup hand-off in `scratch`: not part of the product library."""
     _, kind, scalar = stat
@@ -332,6 +360,8 @@ def attention(q, k, v, heads, scale, bias=None, bias_coeff=None, stat=None, scra
     d = _desc(q, k, v, out, heads, scale)
     lib = _lib.load()
     route = _attention_route(bias is not None, stat, scratch, parts, d.M)
+    if route in ("parts", "stat") and stat[0] is None and scratch is None and long_keys(d.M):
+        route = "long"      # by key count alone: the pair of launches of libpww_hip_long.so
     io = (_ptr(q), _ptr(k), _ptr(v), _ptr(out))
     if route != "self":
         bias = _bias_view(bias, d)
@@ -345,6 +375,8 @@ def attention(q, k, v, heads, scale, bias=None, bias_coeff=None, stat=None, scra
             _launch_stat(lib, io, bias, bias_coeff, d, stat, coeff_dev)
         elif route == "parts":
             _launch_parts(lib, io, bias, bias_coeff, d, stat, parts, stats_out, coeff_dev, bias_cols, compact, gated)
+        elif route == "long":
+            _launch_long(io, bias, bias_coeff, d, stat, parts, stats_out, coeff_dev, bias_cols, gated)
         else:
             _launch_fused(io, bias, bias_coeff, d, stat, scratch, q.device, stats_out, coeff_dev, bias_cols, compact, gated)
     return out
@@ -370,8 +402,8 @@ def attention_probs(q, k, heads, scale, bias=None, bias_coeff=None, stat=None, c
     q, k = _prep(q), _prep(k)
     d = _desc(q, k, None, None, heads, scale)
     B, N, M = d.B, d.N, d.M
-    if M > FUSED_MAX_KEYS:
-        raise PwwHipError("attention_probs takes at most %d keys (got %d)" % (FUSED_MAX_KEYS, M))
+    if M > LONG_MAX_KEYS:
+        raise PwwHipError("attention_probs takes at most %d keys (got %d)" % (LONG_MAX_KEYS, M))
     n_img = int(images or 0)
     if n_img < 0 or n_img > B:
         raise PwwHipError("attention_probs: images = %d outside 0 .. B = %d" % (n_img, B))
@@ -396,9 +428,11 @@ def attention_probs(q, k, heads, scale, bias=None, bias_coeff=None, stat=None, c
     pd = ProbsDesc(ctypes.sizeof(ProbsDesc), n_img, int(bool(accumulate)), float(weight))
     pd.out_stride[:] = [out.stride(0), out.stride(1)]
     op = _cross_opts(B, N, coeff_dev, 0, None)
+    lib = _lib.load_long() if long_keys(M) else _lib.load()
+    launch, name = (lib.pww_long_cross_attn_probs, "pww_long_cross_attn_probs") if long_keys(M) else (lib.pww_cross_attn_probs, "pww_cross_attn_probs")
     with torch.cuda.device(q.device):
-        _lib.check(_lib.load().pww_cross_attn_probs(_ptr(q), _ptr(k), _ptr(bias), _ptr(stats), int(kind), float(d.H * N * M), float(scalar), _ptr(bias_coeff),
-                                                    ctypes.byref(d), _opt_ref(op), _ptr(out), ctypes.byref(pd), _stream()), "pww_cross_attn_probs")
+        _lib.check(launch(_ptr(q), _ptr(k), _ptr(bias), _ptr(stats), int(kind), float(d.H * N * M), float(scalar), _ptr(bias_coeff),
+                          ctypes.byref(d), _opt_ref(op), _ptr(out), ctypes.byref(pd), _stream()), name, lib)
     return out
 
 
@@ -534,6 +568,26 @@ def qk_parts(q, k, heads, kind, gate=None, gated=0):
     with torch.cuda.device(q.device):
         _lib.check(lib.pww_qk_parts(_ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), int(gated or 0), _ptr(parts), parts.numel() * 8, _stream()),
                    "pww_qk_parts")
+    return parts
+
+
+def long_qk_parts(q, k, heads, kind, gate=None, gated=0):
+    """qk_parts for FUSED_MAX_KEYS < M <= LONG_MAX_KEYS (pww_long_qk_parts): float64 [B, nparts, 4], the input of attention(..., parts=...)."""
+    _require_gpu(q, k, gate)
+    if q.dtype != k.dtype:
+        raise PwwHipError("long_qk_parts: dtypes differ: %s %s" % (q.dtype, k.dtype))
+    q, k = _prep(q), _prep(k)
+    d = _desc(q, k, None, None, heads, 1.0)
+    lib = _lib.load_long()
+    nparts = int(lib.pww_long_qk_parts_count(ctypes.byref(d)))
+    if nparts <= 0:
+        raise PwwHipError("long_qk_parts: unsupported problem %s x %s, %d heads" % (tuple(q.shape), tuple(k.shape), heads))
+    B = q.shape[0]
+    parts = torch.empty((B, nparts, 4), dtype=torch.float64, device=q.device)
+    gate = _per_image_f32(gate, B, "gate")
+    with torch.cuda.device(q.device):
+        _lib.check(lib.pww_long_qk_parts(_ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), int(gated or 0), _ptr(parts), parts.numel() * 8, _stream()),
+                   "pww_long_qk_parts", lib)
     return parts
 
 
