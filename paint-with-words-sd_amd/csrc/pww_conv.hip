@@ -8,8 +8,14 @@
 // nearest 2x upsample of the input (Upsample2D: the gather reads x[iy >> 1][ix >> 1]) are index arithmetic of the same gather.
 //
 // Tile: 128 (M) x BN (N, 64 or 128) x 64 (K) per 256-thread workgroup, 2 x 2 waves, mfma_f32_16x16x32 with the WEIGHT as the A operand:
-// the accumulator then holds 4 consecutive channels of one pixel per lane (8-byte stores, 8-byte bias / residual loads). Register-staged
-// double buffer, one barrier per K-slab; LDS rows of 128 bytes with the 16-byte chunk index XOR-ed by (row & 7).
+// the accumulator then holds 4 consecutive channels of one pixel per lane (8-byte stores, 8-byte bias / residual loads). LDS rows of 128
+// bytes with the 16-byte chunk index XOR-ed by (row & 7).
+//
+// K loop: CV_PF K-slabs of global loads are in flight while a slab is computed. Slab i waits in register set i % CV_PF and moves to LDS
+// buffer i & 1 (two buffers) after slab i - 1 has been computed, one barrier per slab; the set is requested again (slab i + CV_PF) right
+// after that barrier. The wait ahead of the move is counted (vmcnt = the loads of the CV_PF - 1 younger slabs), never a drain, and the loads
+// stay in flight across the barrier. The steady loop is unrolled CV_PF times and holds no condition, so that the compiler's counts are
+// exact; the last slabs (and splits shorter than 2 CV_PF slabs) go through a drain whose requests and moves are conditional.
 //
 // Split-K (the 16 x 16 and 8 x 8 levels have too few tiles for 256 CUs): each workgroup writes its fp32 partial tile to a caller-owned
 // workspace, a second launch folds the partials in fixed order and applies the epilogue. No atomics, no inter-workgroup waits: results
@@ -24,6 +30,9 @@ namespace pww {
 namespace {
 
 constexpr int CV_BM = 128, CV_THREADS = 256;
+// K-slabs of global loads in flight while one slab is computed. 2 measured 2 - 10 % faster than 1 on every UNet shape at 2 rows; 3 costs
+// 252 VGPRs at BN 128 and the third workgroup per CU at BN 64 and measured no better than 1 (profiles/conv3x3_pipeline.md).
+constexpr int CV_PF = 2;
 
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
@@ -60,11 +69,11 @@ __device__ __forceinline__ void epilogue4(const f32x4 &a, const ConvCold &cold, 
 }
 
 // geo = stride | (upsample << 4). Hot arguments first: 14 dwords preloaded into SGPRs.
-template <typename T, int BN, bool SPLIT>
-__global__ void __launch_bounds__(CV_THREADS) conv3x3_kernel(const T *__restrict__ x, const T *__restrict__ w, void *__restrict__ out, int M, int N,
+template <typename T, int BN>
+__global__ void __launch_bounds__(CV_THREADS, 2) conv3x3_kernel(const T *__restrict__ x, const T *__restrict__ w, void *__restrict__ out, int M, int N,
                                                             int Cin, int Hin, int Win, int Wo, int HWo, const ConvCold cold) {
     typedef typename Vec<T>::v8 V8;
-    constexpr int BM = CV_BM, XL = BM * 8 / CV_THREADS, WL = BN * 8 / CV_THREADS, RM = 4, RN = BN / 32;
+    constexpr int BM = CV_BM, PF = CV_PF, XL = BM * 8 / CV_THREADS, WL = BN * 8 / CV_THREADS, RM = 4, RN = BN / 32;
     constexpr int XBYTES = BM * 128, STAGE = (BM + BN) * 128;
     __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
 
@@ -75,10 +84,10 @@ __global__ void __launch_bounds__(CV_THREADS) conv3x3_kernel(const T *__restrict
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
     const int ntm = (M + BM - 1) / BM;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile = SPLIT ? bid / cold.nsplit : bid, ks = SPLIT ? bid % cold.nsplit : 0;
+    const bool split = cold.nsplit > 1;                     // (uniform: one code object serves both, the partial store is its only other trace)
+    const int tile = bid / cold.nsplit, ks = bid - tile * cold.nsplit;
     const int tm = tile % ntm, tn = tile / ntm;
-    const int s_begin = SPLIT ? (int)((long)ks * nslab / cold.nsplit) : 0;
-    const int s_end = SPLIT ? (int)((long)(ks + 1) * nslab / cold.nsplit) : nslab;
+    const int s_begin = (int)((long)ks * nslab / cold.nsplit), s_end = (int)((long)(ks + 1) * nslab / cold.nsplit);
     const int K9 = 9 * Cin;
 
     // the gather geometry of this thread's XL rows (row (tid >> 3) + 32 i, 16-byte chunk tid & 7 of the slab)
@@ -96,33 +105,37 @@ __global__ void __launch_bounds__(CV_THREADS) conv3x3_kernel(const T *__restrict
     const T *wrow = w + (long)(tn * BN + (tid >> 3)) * K9 + c * 8;
     const int swz = ((c ^ ((tid >> 3) & 7)) << 4);          // LDS byte offset of this thread's chunk within its row
 
-    u32x4 xr[XL], wr[WL];
-    unsigned xok = 0;
+    // PF register sets, one K-slab of global loads each: set p holds slab i + p (mod PF) while slab i is computed
+    u32x4 xr[PF][XL], wr[PF][WL];
+    unsigned xok[PF];
     int tap = s_begin / (Cin >> 6), ci0 = (s_begin - tap * (Cin >> 6)) << 6;
-    auto load = [&](int s) {
+    const T *wnext = wrow + s_begin * 64;
+    auto load = [&](int p) {                               // the next slab in K order into set p
         const int ky = tap / 3, kx = tap - ky * 3;
+        xok[p] = 0;
 #pragma unroll
         for (int i = 0; i < XL; ++i) {
             const int iyv = y0[i] + ky, ixv = x0[i] + kx;
             const bool ok = (unsigned)iyv < (unsigned)Hv && (unsigned)ixv < (unsigned)Wv;
             const int iy = ok ? iyv >> up : 0, ix = ok ? ixv >> up : 0;
-            xr[i] = *reinterpret_cast<const u32x4 *>(x + (unsigned)((pix[i] + iy * Win + ix) * Cin + ci0 + c * 8));
-            xok = (xok & ~(1u << i)) | ((unsigned)ok << i);
+            xr[p][i] = *reinterpret_cast<const u32x4 *>(x + (unsigned)((pix[i] + iy * Win + ix) * Cin + ci0 + c * 8));
+            xok[p] |= (unsigned)ok << i;
         }
 #pragma unroll
-        for (int j = 0; j < WL; ++j) wr[j] = *reinterpret_cast<const u32x4 *>(wrow + (long)(32 * j) * K9 + s * 64);
+        for (int j = 0; j < WL; ++j) wr[p][j] = *reinterpret_cast<const u32x4 *>(wnext + (long)(32 * j) * K9);
+        wnext += 64;
         ci0 += 64;
         if (ci0 == Cin) { ci0 = 0; ++tap; }
     };
-    auto store = [&](int buf) {
+    auto store = [&](int p, int buf) {
         char *base = lds + buf * STAGE;
 #pragma unroll
         for (int i = 0; i < XL; ++i) {
             const u32x4 z = {0u, 0u, 0u, 0u};           // (the halo's select sits here, after the compute: the loads stay in flight across it)
-            *reinterpret_cast<u32x4 *>(base + ((tid >> 3) + 32 * i) * 128 + swz) = (xok >> i) & 1u ? xr[i] : z;
+            *reinterpret_cast<u32x4 *>(base + ((tid >> 3) + 32 * i) * 128 + swz) = (xok[p] >> i) & 1u ? xr[p][i] : z;
         }
 #pragma unroll
-        for (int j = 0; j < WL; ++j) *reinterpret_cast<u32x4 *>(base + XBYTES + ((tid >> 3) + 32 * j) * 128 + swz) = wr[j];
+        for (int j = 0; j < WL; ++j) *reinterpret_cast<u32x4 *>(base + XBYTES + ((tid >> 3) + 32 * j) * 128 + swz) = wr[p][j];
     };
 
     f32x4 acc[RN][RM];
@@ -132,22 +145,15 @@ __global__ void __launch_bounds__(CV_THREADS) conv3x3_kernel(const T *__restrict
         for (int i = 0; i < RM; ++i) acc[r][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int fr = lane & 15, fq = lane >> 4;
-    if (s_begin < s_end) {
-        load(s_begin);
-        store(0);
-        __syncthreads();
-    }
-    for (int s = s_begin; s < s_end; ++s) {
-        const int cur = (s - s_begin) & 1;
-        if (s + 1 < s_end) load(s + 1);
-        const char *bx = lds + cur * STAGE, *bw = bx + XBYTES;
+    auto compute = [&](int buf) {
+        const char *bx = lds + buf * STAGE, *bw = bx + XBYTES;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             V8 xf[RM], wf[RN];
 #pragma unroll
-            for (int i = 0; i < RM; ++i) {
-                const int row = wm * 64 + i * 16 + fr;
-                xf[i] = *reinterpret_cast<const V8 *>(bx + row * 128 + (((kk * 4 + fq) ^ (row & 7)) << 4));
+            for (int q = 0; q < RM; ++q) {
+                const int row = wm * 64 + q * 16 + fr;
+                xf[q] = *reinterpret_cast<const V8 *>(bx + row * 128 + (((kk * 4 + fq) ^ (row & 7)) << 4));
             }
 #pragma unroll
             for (int r = 0; r < RN; ++r) {
@@ -157,10 +163,41 @@ __global__ void __launch_bounds__(CV_THREADS) conv3x3_kernel(const T *__restrict
 #pragma unroll
             for (int r = 0; r < RN; ++r)
 #pragma unroll
-                for (int i = 0; i < RM; ++i) acc[r][i] = mfma16(wf[r], xf[i], acc[r][i]);
+                for (int q = 0; q < RM; ++q) acc[r][q] = mfma16(wf[r], xf[q], acc[r][q]);
         }
-        if (s + 1 < s_end) store(cur ^ 1);
-        __syncthreads();
+    };
+
+    // Slab i of this workgroup's n (>= 1: the host never plans more splits than slabs) lives in register set i % PF until it moves to LDS
+    // buffer i & 1. Prologue: slabs 0 .. PF - 1 are requested, slab 0 lands in LDS (its wait counts past the younger sets' loads).
+    const int n = s_end - s_begin;
+    load(0);
+#pragma unroll
+    for (int p = 1; p < PF; ++p)
+        if (p < n) load(p);
+    store(0, 0);
+    __syncthreads();
+    // Slab i: request slab i + PF into the set slab i came from, compute slab i from LDS, move slab i + 1 (requested PF - 1 slabs ago) from
+    // its registers to the other LDS buffer, one barrier. The wait ahead of that move leaves the PF - 1 younger slabs in flight, across the
+    // barrier too. The steady loop is free of conditions: every load and every move in it happens, so the compiler's wait counts are exact.
+    int i = 0;
+    for (; i + 2 * PF <= n; i += PF) {
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            load(p);
+            compute((i + p) & 1);
+            store((p + 1) % PF, (i + p + 1) & 1);
+            __syncthreads();
+        }
+    }
+    // drain: the last PF .. 2 PF - 1 slabs (or all of a short split), each request and move under its own condition
+#pragma unroll
+    for (int t = 0; t < 2 * PF - 1; ++t) {
+        if (i + t < n) {
+            if (i + t + PF < n) load(t % PF);
+            compute((i + t) & 1);
+            if (i + t + 1 < n) store((t + 1) % PF, (i + t + 1) & 1);
+            __syncthreads();
+        }
     }
 
     // lane holds D[n = 16 r + 4 fq + j][m = 16 i + fr] of its wave's sub-tile
@@ -171,7 +208,7 @@ __global__ void __launch_bounds__(CV_THREADS) conv3x3_kernel(const T *__restrict
 #pragma unroll
         for (int r = 0; r < RN; ++r) {
             const int n = tn * BN + wn * (BN / 2) + r * 16 + fq * 4;
-            if (SPLIT) *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(out) + ((long)ks * M + m) * N + n) = acc[r][i];
+            if (split) *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(out) + ((long)ks * M + m) * N + n) = acc[r][i];
             else epilogue4<T>(acc[r][i], cold, reinterpret_cast<T *>(out), (long)m * N + n, n);
         }
     }
@@ -189,15 +226,15 @@ __global__ void __launch_bounds__(256) conv3x3_fold_kernel(const float *__restri
 }
 
 // Tile width and K split per GEMM shape (M = B Ho Wo, N = Cout, K-slabs = 9 Cin / 64), measured on MI355X (tools/time_conv3x3.py --sweep,
-// profiles/conv3x3_sweep.md): the SD1.5 UNet's convolutions at 2 and 16 rows. The fastest split keeps ~15 K-slabs per workgroup and
+// profiles/conv3x3_sweep_v2.md; conv3x3_sweep.md is the table of the one-slab loop): the SD1.5 UNet's convolutions at 2 and 16 rows. The fastest split keeps ~15 K-slabs per workgroup and
 // 2 - 4 workgroups per CU; shapes not listed take the rule below (about 480 workgroups, at least 8 K-slabs per split).
 struct ConvTune { int M, N, nslab, bn, nsplit; };
 constexpr ConvTune CONV_TUNED[] = {
     // 2 rows (batch 1 with classifier-free guidance)
-    {8192, 320, 45, 64, 2}, {8192, 320, 90, 64, 4}, {8192, 320, 135, 64, 3}, {8192, 640, 90, 128, 3},
+    {8192, 320, 45, 64, 3}, {8192, 320, 90, 64, 4}, {8192, 320, 135, 64, 3}, {8192, 640, 90, 128, 3},
     {2048, 320, 45, 64, 6}, {2048, 640, 45, 64, 3}, {2048, 640, 90, 128, 6}, {2048, 640, 135, 128, 6}, {2048, 640, 180, 128, 6},
     {2048, 640, 270, 128, 6}, {2048, 1280, 180, 128, 3},
-    {512, 640, 90, 64, 6}, {512, 1280, 90, 64, 6}, {512, 1280, 180, 128, 12}, {512, 1280, 270, 128, 12}, {512, 1280, 360, 128, 12},
+    {512, 640, 90, 64, 6}, {512, 1280, 90, 128, 6}, {512, 1280, 180, 128, 12}, {512, 1280, 270, 128, 12}, {512, 1280, 360, 128, 12},
     {128, 1280, 180, 64, 12}, {128, 1280, 360, 64, 24},
     // 16 rows (batch 8)
     {65536, 640, 90, 128, 1}, {16384, 1280, 180, 128, 1},
@@ -250,13 +287,10 @@ int conv_launch(const ConvPlan &p, const pww_conv_desc_t *d, const void *x, cons
     const T *xt = static_cast<const T *>(x), *wt = static_cast<const T *>(w);
     const int N = d->Cout, HWo = p.Ho * p.Wo;
     const dim3 grid(p.ntiles * p.nsplit), block(CV_THREADS);
-    if (p.nsplit == 1) {
-        if (p.bn == 128) launch_timed(conv3x3_kernel<T, 128, false>, grid, block, 0, stream, xt, wt, y, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
-        else launch_timed(conv3x3_kernel<T, 64, false>, grid, block, 0, stream, xt, wt, y, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
-        return check_hip(hipGetLastError(), "conv3x3 launch");
-    }
-    if (p.bn == 128) launch_timed(conv3x3_kernel<T, 128, true>, grid, block, 0, stream, xt, wt, ws, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
-    else launch_timed(conv3x3_kernel<T, 64, true>, grid, block, 0, stream, xt, wt, ws, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
+    void *out = p.nsplit == 1 ? y : ws;
+    if (p.bn == 128) launch_timed(conv3x3_kernel<T, 128>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
+    else launch_timed(conv3x3_kernel<T, 64>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
+    if (p.nsplit == 1) return check_hip(hipGetLastError(), "conv3x3 launch");
     const long MN = (long)p.M * N, n4 = MN / 4;
     launch_timed(conv3x3_fold_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, static_cast<const float *>(ws), static_cast<T *>(y), n4,
                  N, MN, cold);
