@@ -158,8 +158,12 @@ int pww_cross_attn_fwd_stat(const void *q, const void *k, const void *v, void *o
  *   gated_images      (version >= 121; the field was padding before) the caller's hint that gate[b] != 0 exactly for b < gated_images
  *                     -- a CFG-folded batch [conditional rows; unconditional rows] (paint_with_words.py:479-489 as one call). The
  *                     gated-in images carry the statistic, the hand-off and the bias work; the launch gives them more, shorter
- *                     workgroups so that all workgroups finish together. 0 = unknown. A wrong hint costs time, never correctness:
- *                     the kernel still reads gate[].
+ *                     workgroups so that all workgroups finish together. 0 = no such split: EVERY image may be biased (negative
+ *                     regions: the unconditional rows carry a map and a non-zero coefficient of their own), all images get the same
+ *                     share of the grid. A wrong hint costs time, never correctness: the kernel still reads gate[].
+ *   The row coefficient (`bias_coeff` / `gate` of the launches below) may be ANY finite value, not only 0 or 1: it is a factor of
+ *   c[b] = coeff_scalar * stat(stats[b]) * gate[b]. Exactly 0 means "this image takes no bias": no statistic is formed or folded for it
+ *   and its partials / stats_out rows are left untouched; every other value is multiplied in, in fp32, in the order written here.
  */
 typedef struct pww_cross_opts {
     uint32_t size;
@@ -234,7 +238,8 @@ int pww_cross_attn_fwd_parts(const void *q, const void *k, const void *v, void *
  *   gate      fp32 [B] or NULL: images with gate[b] == 0 get no partials (their rows of `partials` are left untouched)
  *   stat_kind PWW_STAT_* (PWW_STAT_ALL: all four fields): only the fields that statistic is made of are formed, the others hold the
  *             neutral element
- *   gated_images  the caller's hint that gate[b] != 0 exactly for b < gated_images (0 = unknown): the grid then covers those images only
+ *   gated_images  the caller's hint that gate[b] != 0 exactly for b < gated_images: the grid then covers those images only. 0 = every
+ *             image may have a non-zero gate (of any finite value): the grid covers all B, images whose gate is 0 write nothing
  *   partials  double [B][pww_qk_parts_count(desc)][4] = { max, min, sum, sum of squares }, 16-byte aligned: the input of
  *             pww_cross_attn_fwd_parts
  * Sums accumulate in fp32 over a lane's 16 scores and in fp64 from there (within 1e-6, relative, of pww_qk_reduce).

@@ -39,7 +39,8 @@ const char *pww_long_last_error(void);
  * the four waves of a workgroup share one partial.
  *   q, k          as described by the attention descriptor: dtype, B / H / N / M / D and the q / k strides are read
  *   gate          fp32 [B] or NULL: images with gate[b] == 0 get no partials (their rows of `partials` are left untouched)
- *   gated_images  hint that gate[b] != 0 exactly for b < gated_images (0 = unknown): the grid then covers those images only
+ *   gated_images  hint that gate[b] != 0 exactly for b < gated_images: the grid then covers those images only. 0 = every image may have
+ *                 a non-zero gate (negative regions bias the unconditional rows too): the grid covers all B
  *   partials      16-byte aligned, partials_bytes >= B * nparts * 32
  * Sums accumulate in fp32 over a lane's 16 scores and in fp64 from there: within 1e-6, relative to the largest score, of pww_qk_reduce.
  */
@@ -52,7 +53,8 @@ int32_t pww_long_qk_parts_count(const pww_attn_desc_t *desc);
  *   c[b] = coeff_scalar * stat(fold(partials[b][0 .. nparts-1])) * gate[b]
  * `stats_out` (optional, double [B][4]) receives the folded fields. Of `opts` (NULL: none) coeff_scalar_dev (a device word that replaces
  * coeff_scalar when the kernel runs: one captured hipGraph for all denoise steps), bias_cols (columns >= bias_cols of the map are zero)
- * and gated_images are read; the compact form of the map is not taken (PWW_ENOTSUP).
+ * and gated_images are read; the compact form of the map is not taken (PWW_ENOTSUP). gate[b] may be any finite value (a factor of the
+ * image's coefficient; exactly 0 = the image takes no bias and reads no partials), and gated_images == 0 means every image is biased.
  * bias: a dense fp32 map with unit key stride (bias_stride[3] == 1), required. D a multiple of 8 up to PWW_MAX_HEAD_DIM, f16 / bf16, any N.
  * One 128-row query block per workgroup; K / V in 128-key stages through LDS (both resident for D <= 96, walked in turn above), the wave's
  * bias rows staged per 64-key tile, the online softmax steps between tiles.

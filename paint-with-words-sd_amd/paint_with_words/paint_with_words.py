@@ -20,7 +20,7 @@ from PIL import Image
 
 import pww_hip
 from pww_hip.attention import inj_forward  # noqa: F401  (same import path as the reference's symbol)
-from pww_hip.conditioning import check_prompt_chunks, prompt_chunk_count
+from pww_hip.conditioning import check_prompt_chunks, prompt_chunk_count, check_negative_context
 from pww_hip.conditioning import (always_round, _extract_seed_and_sigma_from_context, _encode_text_color_inputs,  # noqa: F401
                                   _get_binary_mask, gaussian_blur_mask)
 from pww_hip.sampler import PwWSampler, initial_latents
@@ -110,21 +110,32 @@ def _batch_prompt_chunks(tokenizer, prompts, max_prompt_chunks):
     return max(prompt_chunk_count(tokenizer, p, max_prompt_chunks) for p in prompts)
 
 
+def _negative_contexts(negative_color_contexts, n, color_map_images):
+    """-> ([one negative_color_context or None per request], does any request carry one). A request without a color map has no regions
+    on either side."""
+    negs = list(negative_color_contexts) if negative_color_contexts is not None else [None] * n
+    negs = [c if (c and color_map_images[i] is not None) else None for i, c in enumerate(negs)]
+    return negs, any(c is not None for c in negs)
+
+
 def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale,
               weight_function, unconditional_input_prompt, init_images=None, strength=0.5, latent_hw=None,
-              on_step=None, use_region_sigma=True, shared=False, max_prompt_chunks=1):
+              on_step=None, use_region_sigma=True, shared=False, max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0):
     """Shared body of paint_with_words / paint_with_words_batch / the pipeline class (reference :414-506): conditioning
     per request (once if every request shares map, context and prompt), CPU-generated latents per seed exactly as :446,
-    one denoise loop over all images. Returns the final latents [n, 4, h, w]."""
+    one denoise loop over all images. Returns the final latents [n, 4, h, w]. negative_color_contexts: None, or one dict (or None) per
+    request like color_contexts -- regions of the unconditional prompt (see paint_with_words)."""
     vae, unet, text_encoder, tokenizer, scheduler = tools
     n = len(seeds)
     sampler = _sampler_for(unet, scheduler, DEFAULT_MODE)   # also installs the attention plug
     conds, unconds, seeds_info = [], [], []
-    min_chunks = _batch_prompt_chunks(tokenizer, prompts[:1] if shared else prompts, max_prompt_chunks)
+    min_chunks = _batch_prompt_chunks(tokenizer, (prompts[:1] if shared else prompts) + [unconditional_input_prompt], max_prompt_chunks)
+    negs, any_neg = _negative_contexts(negative_color_contexts, n, color_map_images)
     for i in range(1 if shared else n):
         extra_seeds, region_info, cond, uncond = _encode_text_color_inputs(
             text_encoder, tokenizer, device, color_map_images[i], color_contexts[i], prompts[i], unconditional_input_prompt,
-            dtype=_unet_dtype(unet), use_sigma=use_region_sigma, max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks)
+            dtype=_unet_dtype(unet), use_sigma=use_region_sigma, max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks,
+            negative_color_context=negs[i], negative_maps=any_neg)
         conds.append(cond), unconds.append(uncond), seeds_info.append((extra_seeds, region_info))
     if shared:
         conds, unconds, seeds_info = conds[0], unconds[0], seeds_info * n
@@ -154,7 +165,8 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
         latents = torch.cat(lats, dim=0)
 
     with pww_hip.miopen_find():
-        return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, on_step=on_step)
+        return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, on_step=on_step,
+                              negative_strength=negative_strength)
 
 
 @torch.no_grad()
@@ -176,20 +188,28 @@ def paint_with_words(
     init_image: Optional[Image.Image] = None,
     strength: float = 0.5,
     return_latents: bool = False,
+    negative_color_context: Optional[Dict[Tuple[int, int, int], str]] = None,
+    negative_strength: float = 1.0,
     max_prompt_chunks: int = 1,
 ):
     """reference :391-510. `return_latents=True` (extension) returns the final latent tensor instead
-    of decoding it -- the quantity parity is checked on. `max_prompt_chunks` (extension; 1, 2 or 3): a prompt longer than 75 tokens is
+    of decoding it -- the quantity parity is checked on. `negative_color_context` (extension; the reference's README lists "negative
+    region" as an open item): regions of the UNCONDITIONAL prompt, in the grammar of color_context ("phrase,strength[,-1[,sigma]]", a region
+    seed is refused) and read against the same color map; the phrases are looked up in `unconditional_input_prompt`. The unconditional
+    evaluation of every step then adds `negative_strength * weight_function(w_neg, sigma, qk_uncond)` to its cross-attention scores, so
+    classifier-free guidance pushes away from the phrase inside its region. None / {} (the default) is the reference's unconditional pass.
+    The dict is stripped of its seed / sigma tails like color_context. `max_prompt_chunks` (extension; 1, 2 or 3): a prompt longer than 75 tokens is
     encoded in up to that many 75-token chunks (154 / 231 keys) instead of cut at 77; with the default every request is tokenized as in
     the reference, and a prompt that needs fewer chunks than the cap gets only the chunks it needs."""
     check_prompt_chunks(max_prompt_chunks)
+    check_negative_context(negative_color_context, negative_strength)
     color_map_image.size     # the reference dereferences it unconditionally (:414): None raises here too
     tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
                             model_token=model_token) if preloaded_utils is None else preloaded_utils)
     latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps,
                         guidance_scale, weight_function, unconditional_input_prompt,
                         init_images=None if init_image is None else [init_image], strength=strength, shared=True,
-                        max_prompt_chunks=max_prompt_chunks)
+                        max_prompt_chunks=max_prompt_chunks, negative_color_contexts=[negative_color_context], negative_strength=negative_strength)
     if return_latents:
         return _sampler_for(tools[1], tools[4], DEFAULT_MODE).checked(latents)
     image = _pil_from_latents(tools[0], latents)[0]
@@ -216,6 +236,8 @@ def paint_with_words_batch(
     init_images: Union[None, Image.Image, Sequence[Image.Image]] = None,
     strength: float = 0.5,
     return_latents: bool = False,
+    negative_color_context: Union[None, Dict, Sequence[Optional[Dict]]] = None,
+    negative_strength: float = 1.0,
     max_prompt_chunks: int = 1,
 ):
     """len(seeds) requests through ONE denoise loop (the reference's multi-sample path is a
@@ -225,28 +247,33 @@ def paint_with_words_batch(
     statistic and region seeds, so image i equals `paint_with_words(color_contexts[i], color_map_images[i],
     input_prompts[i], seed=seeds[i], ...)`. All color maps of one call must have the same size. The caller's
     color_context dicts are mutated like the single-image call mutates its dict (:296). Returns a list of PIL images
-    (or the [n, 4, h, w] latents with return_latents=True). max_prompt_chunks: see paint_with_words; with per-image prompts every image
-    is padded (with empty chunks) to the largest chunk count of the batch."""
+    (or the [n, 4, h, w] latents with return_latents=True). negative_color_context / negative_strength: see paint_with_words; one dict
+    shared by every request or one (or None) per seed, like color_contexts. max_prompt_chunks: see paint_with_words; with per-image prompts
+    every image is padded (with empty chunks) to the largest chunk count of the batch."""
     check_prompt_chunks(max_prompt_chunks)
+    check_negative_context(negative_color_context, negative_strength)
     seeds = list(seeds)
     n = len(seeds)
     if n == 0:
         return []
     ctxs, s1 = _broadcast(color_contexts, n, "color_context")
+    negs, s4 = _broadcast(negative_color_context, n, "negative_color_context")
     maps, s2 = _broadcast(color_map_images, n, "color_map_images")
     prompts, s3 = _broadcast(input_prompts, n, "input_prompts")
     inits = None if init_images is None else _broadcast(init_images, n, "init_images")[0]
     if len({m.size for m in maps}) != 1:
         raise ValueError("paint_with_words_batch: all color maps of one call must have the same size, got %s"
                          % sorted({m.size for m in maps}))
-    shared = s1 and s2 and s3
-    originals = ctxs
+    shared = s1 and s2 and s3 and s4
+    originals = ctxs + [c for c in negs if c]
     if not shared:       # one dict may serve several requests: parse a private copy per request, strip the caller's afterwards
         ctxs = [dict(c) for c in ctxs]
+        negs = [dict(c) if c else None for c in negs]
     tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
                             model_token=model_token) if preloaded_utils is None else preloaded_utils)
     latents = _generate(tools, device, ctxs, maps, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
-                        unconditional_input_prompt, init_images=inits, strength=strength, shared=shared, max_prompt_chunks=max_prompt_chunks)
+                        unconditional_input_prompt, init_images=inits, strength=strength, shared=shared, max_prompt_chunks=max_prompt_chunks,
+                        negative_color_contexts=negs, negative_strength=negative_strength)
     if not shared:
         for c in {id(c): c for c in originals}.values():
             _extract_seed_and_sigma_from_context(c)

@@ -15,7 +15,8 @@ from pww_hip import ops
 _pw_module_name = __name__.rsplit(".", 1)[0] + ".paint_with_words"      # the function-API module: its DEFAULT_MODE is read at call time
 from .paint_with_words import (LMSDiscreteScheduler, pww_load_tools, preprocess, _pil_from_latents,
                                _encode_text_color_inputs, _sampler_for, _unet_dtype, _broadcast, _batch_prompt_chunks,
-                               check_prompt_chunks)
+                               check_prompt_chunks, check_negative_context, _negative_contexts,
+                               _extract_seed_and_sigma_from_context)
 
 
 def _mode():
@@ -116,14 +117,16 @@ def _inpaint_inputs(vae, init_image, mask_image, seed, scheduler, timesteps, dev
 
 def _generate_inpaint(tools, device, color_contexts, color_map_images, mask_images, init_images, prompts, seeds,
                       num_inference_steps, guidance_scale, weight_function, unconditional_input_prompt, strength, shared,
-                      on_step=None, mask_hw=None, resize_inputs=True, use_region_sigma=True, max_prompt_chunks=1):
+                      on_step=None, mask_hw=None, resize_inputs=True, use_region_sigma=True, max_prompt_chunks=1,
+                      negative_color_contexts=None, negative_strength=1.0):
     """Shared body of paint_with_words_inpaint / _batch / the inpaint pipeline class. The function API resizes color map and
     mask to the init image (:172-173, `resize_inputs`); the pipeline class does not and sizes the latent mask by `mask_hw`."""
     vae, unet, text_encoder, tokenizer, scheduler = tools
     n = len(seeds)
     sampler = _sampler_for(unet, scheduler, _mode())
     conds, unconds = [], []
-    min_chunks = _batch_prompt_chunks(tokenizer, prompts[:1] if shared else prompts, max_prompt_chunks)
+    min_chunks = _batch_prompt_chunks(tokenizer, (prompts[:1] if shared else prompts) + [unconditional_input_prompt], max_prompt_chunks)
+    negs, any_neg = _negative_contexts(negative_color_contexts, n, color_map_images)
     for i in range(1 if shared else n):
         width, height = init_images[i].size
         color_map = color_map_images[i]
@@ -131,7 +134,8 @@ def _generate_inpaint(tools, device, color_contexts, color_map_images, mask_imag
             color_map = color_map.resize((width, height), Image.NEAREST)            # :172
         _, _, cond, uncond = _encode_text_color_inputs(text_encoder, tokenizer, device, color_map, color_contexts[i], prompts[i],
                                                        unconditional_input_prompt, dtype=_unet_dtype(unet), use_sigma=use_region_sigma,
-                                                       max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks)
+                                                       max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks,
+                                                       negative_color_context=negs[i], negative_maps=any_neg)
         conds.append(cond), unconds.append(uncond)
     if shared:
         conds, unconds = conds[0], unconds[0]
@@ -160,7 +164,8 @@ def _generate_inpaint(tools, device, color_contexts, color_map_images, mask_imag
             f"channels but received {n_lat} latent + 1 mask + {n_extra - 1} masked-image latent channels = {n_lat + n_extra}. "
             "Please verify the config of `pipeline.unet` or your `mask_image` or `image` input.")
     with pww_hip.miopen_find():
-        return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra, on_step=on_step)
+        return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra, on_step=on_step,
+                              negative_strength=negative_strength)
 
 
 @torch.no_grad()
@@ -183,15 +188,19 @@ def paint_with_words_inpaint(
     model_token: Optional[str] = None,
     strength: float = 1.0,
     return_latents: bool = False,
+    negative_color_context: Optional[Dict[Tuple[int, int, int], str]] = None,
+    negative_strength: float = 1.0,
     max_prompt_chunks: int = 1,
 ):
-    """reference :137-270. max_prompt_chunks (extension): see paint_with_words."""
+    """reference :137-270. negative_color_context / negative_strength / max_prompt_chunks (extensions): see paint_with_words."""
     check_prompt_chunks(max_prompt_chunks)
+    check_negative_context(negative_color_context, negative_strength)
     tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
                             model_token=model_token) if preloaded_utils is None else preloaded_utils)
     latents = _generate_inpaint(tools, device, [color_context], [color_map_image], [mask_image], [init_image], [input_prompt],
                                 [seed], num_inference_steps, guidance_scale, weight_function, unconditional_input_prompt,
-                                strength, shared=True, max_prompt_chunks=max_prompt_chunks)
+                                strength, shared=True, max_prompt_chunks=max_prompt_chunks,
+                                negative_color_contexts=[negative_color_context], negative_strength=negative_strength)
     if return_latents:
         return _sampler_for(tools[1], tools[4], _mode()).checked(latents)
     image = _pil_from_latents(tools[0], latents)[0]
@@ -219,12 +228,16 @@ def paint_with_words_inpaint_batch(
     model_token: Optional[str] = None,
     strength: float = 1.0,
     return_latents: bool = False,
+    negative_color_context: Union[None, Dict, Sequence[Optional[Dict]]] = None,
+    negative_strength: float = 1.0,
     max_prompt_chunks: int = 1,
 ):
     """len(seeds) inpainting requests through one denoise loop (see paint_with_words_batch): each of the image-like
     arguments and the prompt is one shared value or a sequence with one entry per seed; all init images of a call must
-    have the same size. Image i equals the single-request call on request i. max_prompt_chunks: see paint_with_words_batch."""
+    have the same size. Image i equals the single-request call on request i. negative_color_context / negative_strength /
+    max_prompt_chunks: see paint_with_words_batch."""
     check_prompt_chunks(max_prompt_chunks)
+    check_negative_context(negative_color_context, negative_strength)
     seeds = list(seeds)
     n = len(seeds)
     if n == 0:
@@ -236,13 +249,19 @@ def paint_with_words_inpaint_batch(
     prompts, s3 = _broadcast(input_prompts, n, "input_prompts")
     if len({im.size for im in inits}) != 1:
         raise ValueError("paint_with_words_inpaint_batch: all init images of one call must have the same size")
-    if not (s1 and s2 and s3):
+    negs, s4 = _broadcast(negative_color_context, n, "negative_color_context")
+    originals = [c for c in negs if c]
+    if not (s1 and s2 and s3 and s4):
         ctxs = [dict(c) for c in ctxs]
+        negs = [dict(c) if c else None for c in negs]
     tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
                             model_token=model_token) if preloaded_utils is None else preloaded_utils)
     latents = _generate_inpaint(tools, device, ctxs, maps, masks, inits, prompts, seeds, num_inference_steps, guidance_scale,
-                                weight_function, unconditional_input_prompt, strength, shared=s1 and s2 and s3,
-                                max_prompt_chunks=max_prompt_chunks)
+                                weight_function, unconditional_input_prompt, strength, shared=s1 and s2 and s3 and s4,
+                                max_prompt_chunks=max_prompt_chunks, negative_color_contexts=negs, negative_strength=negative_strength)
+    if not (s1 and s2 and s3 and s4):      # (private copies were parsed: strip the caller's negative dicts, as the single-request call does)
+        for c in {id(c): c for c in originals}.values():
+            _extract_seed_and_sigma_from_context(c)
     if return_latents:
         return _sampler_for(tools[1], tools[4], _mode()).checked(latents)
     images = _pil_from_latents(tools[0], latents)

@@ -26,7 +26,8 @@ from PIL import Image
 import pww_hip
 import importlib
 _pw = importlib.import_module(__name__.rsplit(".", 1)[0] + ".paint_with_words")
-from .paint_with_words import (pww_load_tools, LMSDiscreteScheduler, _generate, _pil_from_latents, _sampler_for, check_prompt_chunks)
+from .paint_with_words import (pww_load_tools, LMSDiscreteScheduler, _generate, _pil_from_latents, _sampler_for, check_prompt_chunks,
+                               check_negative_context)
 from . import paint_with_words_inpaint as _inp
 
 _warned = set()
@@ -51,6 +52,10 @@ class PaintWithWord_StableDiffusionPipeline:
     # extension: `pipe.max_prompt_chunks = 2` / `3` encodes a prompt of more than 75 tokens in that many 75-token chunks at the most (see
     # paint_with_words). An attribute, because the constructor and `__call__` keep exactly the reference's parameter lists.
     max_prompt_chunks = 1
+    # extension: negative regions (see paint_with_words): `pipe.negative_color_context = {(r, g, b): "phrase,strength"}` -- phrases of
+    # `negative_prompt`, read against the call's color map -- and `pipe.negative_strength`. Attributes for the same reason.
+    negative_color_context = None
+    negative_strength = 1.0
 
     def __init__(self, vae, text_encoder, tokenizer, unet, scheduler=None, safety_checker=None, feature_extractor=None,
                  requires_safety_checker: bool = False):
@@ -128,6 +133,7 @@ class PaintWithWord_StableDiffusionPipeline:
     ):
         """reference :629-842 (same parameter list, order and defaults). Prompts longer than 75 tokens: `self.max_prompt_chunks`."""
         max_prompt_chunks = check_prompt_chunks(self.max_prompt_chunks)
+        check_negative_context(self.negative_color_context, self.negative_strength)
         height = height or self._default_side()
         width = width or self._default_side()
         if height % 8 or width % 8:                                   # check_inputs of the diffusers base class
@@ -147,7 +153,8 @@ class PaintWithWord_StableDiffusionPipeline:
         lat = _generate(self._tools(), str(self.device), [color_context], [color_map_image], [prompt], [seed], num_inference_steps,
                         guidance_scale, weight_function, negative_prompt or "", init_images=None if image is None else [image],
                         strength=eta, latent_hw=(height, width), use_region_sigma=False, shared=True,
-                        on_step=self._callback_adapter(callback, callback_steps), max_prompt_chunks=max_prompt_chunks)
+                        on_step=self._callback_adapter(callback, callback_steps), max_prompt_chunks=max_prompt_chunks,
+                        negative_color_contexts=[self.negative_color_context], negative_strength=self.negative_strength)
         images = _decode(self.vae, lat, output_type)
         _sampler_for(self.unet, self.scheduler, _pw.DEFAULT_MODE).check_errors()
         if not return_dict:
@@ -183,6 +190,7 @@ class PaintWithWord_StableDiffusionInpaintPipeline(PaintWithWord_StableDiffusion
         """reference paint_with_words_inpaint.py:340-575 (same parameter list, order and defaults). Prompts longer than 75 tokens:
         `self.max_prompt_chunks`."""
         max_prompt_chunks = check_prompt_chunks(self.max_prompt_chunks)
+        check_negative_context(self.negative_color_context, self.negative_strength)
         if image is None or mask_image is None:
             raise ValueError("`image` and `mask_image` are required for inpainting")
         height = height or self._default_side()                      # :427-428
@@ -202,7 +210,8 @@ class PaintWithWord_StableDiffusionInpaintPipeline(PaintWithWord_StableDiffusion
         lat = _inp._generate_inpaint(self._tools(), str(self.device), [color_context], [color_map_image], [mask_image], [image], [prompt],
                                      [seed], num_inference_steps, guidance_scale, weight_function, negative_prompt or "", eta, shared=True,
                                      on_step=self._callback_adapter(callback, callback_steps), mask_hw=(height, width), resize_inputs=False,
-                                     use_region_sigma=False, max_prompt_chunks=max_prompt_chunks)
+                                     use_region_sigma=False, max_prompt_chunks=max_prompt_chunks,
+                                     negative_color_contexts=[self.negative_color_context], negative_strength=self.negative_strength)
         images = _decode(self.vae, lat, output_type)
         _sampler_for(self.unet, self.scheduler, _pw.DEFAULT_MODE).check_errors()
         if not return_dict:

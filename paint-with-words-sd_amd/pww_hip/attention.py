@@ -28,7 +28,8 @@ COEFF_SLOTS = "_PWW_COEFF_SLOTS"   # private context key: CoeffSlots (hipGraph m
 BIAS_COLS = "_PWW_BIAS_COLS"       # private context key: int, columns >= this of every weight map of the context are zero
 COMPACT_W = "_PWW_COMPACT_W_"      # private context key prefix: compact form [N, R] (or [B, N, R]) of CROSS_ATTENTION_WEIGHT_<N>
 COMPACT_IDX = "_PWW_COMPACT_IDX"   # private context key: int32 [R] (or [B, R]) columns of the compact slots, -1 = unused
-GATED_ROWS = "_PWW_GATED_ROWS"     # private context key: int, _PWW_ROW_GATE is 1 for exactly the first so many rows, 0 after (a CFG-folded batch)
+GATED_ROWS = "_PWW_GATED_ROWS"     # private context key: int, the kernels' work-distribution hint: _PWW_ROW_GATE is non-zero for exactly the first so many rows, 0 after (a CFG-folded batch); 0 = no such split, every row may be biased (negative regions)
+COND_ROWS = "_PWW_COND_ROWS"       # private context key: int, the first so many rows are the conditional ones -- what the attention-map recorder records. Only present when it differs from _PWW_GATED_ROWS (negative regions: the unconditional rows are biased too)
 ATTN_RECORDER = "_PWW_ATTN_RECORDER"   # private context key of CONDITIONAL dicts: attnmaps.AttentionRecorder (pww_hip.record_attention_maps); absent = nothing is recorded
 # Where the score statistic of `weight_function(w, sigma, qk)` is formed (round 5): ALWAYS outside the attention launch -- as partials
 # that the attention launch folds at entry (pww_cross_attn_fwd_parts: nothing waits for another workgroup, nothing has to be resident,
@@ -642,7 +643,7 @@ def _attention(attn, hidden_states, context, out_linear):
     bias = None
     gate = None
     if context is not None and is_dict:
-        gate = context.get(ROW_GATE)   # folded CFG batches: per-row coefficient (1 = cond row, 0 = uncond row)
+        gate = context.get(ROW_GATE)   # folded CFG batches: per-row coefficient (1 = cond row; uncond row: 0, or negative_strength with negative regions)
         f = context["WEIGHT_FUNCTION"]
         n_img = hidden_states.shape[1]
         try:
@@ -793,8 +794,8 @@ def _record_probs(rec, attn, context, query, key, bias, coeff, stat, coeff_dev):
     if M > ops.LONG_MAX_KEYS:
         _warn_once("record_keys", "attention maps: cross-attention over %d > %d keys is not recorded" % (M, ops.LONG_MAX_KEYS))
         return
-    gated = int(context.get(GATED_ROWS, 0) or 0) if context.get(ROW_GATE) is not None else 0
-    tgt = rec.target(attn, B, N, M, gated, query.device)
+    cond_rows = int(context.get(COND_ROWS, 0) or context.get(GATED_ROWS, 0) or 0) if context.get(ROW_GATE) is not None else 0
+    tgt = rec.target(attn, B, N, M, cond_rows, query.device)
     if tgt is None:
         return
     buf, images = tgt

@@ -115,9 +115,10 @@ class AttentionRecorder:
         self.prompts.append(list(token_ids) if content_ids is None else _ChunkedPrompt(token_ids, content_ids, tokenizer.model_max_length - 2))
 
     # -- what the attention plug calls ------------------------------------------------------------
-    def target(self, attn, B, N, M, gated, device):
-        """-> (accumulator rows to add into, images) for one cross-attention call, or None while muted."""
-        images = int(gated) if gated else int(B)
+    def target(self, attn, B, N, M, cond_rows, device):
+        """-> (accumulator rows to add into, images) for one cross-attention call, or None while muted. cond_rows: the first so many of the
+        B rows are the conditional ones of a CFG-folded batch (0: all of them)."""
+        images = int(cond_rows) if cond_rows else int(B)
         if self.images is None:
             self.images = images
         if self.row + images > self.images:

@@ -6,6 +6,8 @@ F.interpolate (:247-276).
 Host side (strings, token matching, the region table) stays Python, as in the reference; function
 names follow the reference's so the call sites read the same.
 """
+import math
+
 import numpy as np
 import torch
 import torch.nn.functional as F  # noqa: F401  (region-seed masks: _get_binary_mask)
@@ -88,6 +90,24 @@ def _extract_seed_and_sigma_from_context(color_context, ignore_seed=-1):
                 extra_seeds[i] = seed
         color_context[k] = ",".join(parts)
     return color_context, extra_seeds, extra_sigmas
+
+
+def check_negative_context(negative_color_context, negative_strength=1.0):
+    """The `negative_color_context` / `negative_strength` keywords of the entry points, checked without touching the caller's dict(s): the
+    grammar of color_context, except that a region seed other than -1 is refused -- region seeding belongs to the initial latent, which the
+    unconditional side does not own."""
+    if isinstance(negative_strength, bool) or not isinstance(negative_strength, (int, float)) or not math.isfinite(float(negative_strength)):
+        raise ValueError("negative_strength must be a finite number (got %r)" % (negative_strength,))
+    if negative_color_context is None:
+        return
+    ctxs = negative_color_context if isinstance(negative_color_context, (list, tuple)) else [negative_color_context]
+    for ctx in ctxs:
+        if ctx is None:
+            continue
+        _, seeds, _ = _extract_seed_and_sigma_from_context(dict(ctx))
+        if seeds:
+            raise ValueError("negative_color_context: a region seed (%s) is not supported on the negative side; write -1, as in "
+                             "\"phrase,strength,-1,sigma\"" % ", ".join(str(v) for v in seeds.values()))
 
 
 def _parse_regions(color_context, tokenizer):
@@ -220,6 +240,13 @@ def build_weight_maps(color_map_rgb, table, token_lis, device, extra_sigmas=None
     return maps
 
 
+def _zero_weight_maps(keys, height, width, n_tokens, device):
+    """The maps of an empty region table (:242-243): all-zero [N, T] per resolution and a thunk for the full-resolution one."""
+    maps = {n: torch.zeros((n, n_tokens), dtype=torch.float32, device=device) for n in keys}
+    maps["ORIG_THUNK"] = lambda: torch.zeros((height, width, n_tokens), dtype=torch.float32, device=device)
+    return maps
+
+
 def _warn_missing_colors(color_map_rgb, table):
     """:233-234."""
     img = np.asarray(color_map_rgb)
@@ -229,7 +256,8 @@ def _warn_missing_colors(color_map_rgb, table):
 
 
 def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, color_context, input_prompt,
-                              unconditional_input_prompt, dtype=None, use_sigma=True, max_prompt_chunks=1, min_prompt_chunks=1):
+                              unconditional_input_prompt, dtype=None, use_sigma=True, max_prompt_chunks=1, min_prompt_chunks=1,
+                              negative_color_context=None, negative_maps=False):
     """:315-388 with the weight maps built by the HIP mask kernel. Returns
     (extra_seeds, seperated_word_contexts, encoder_hidden_states, uncond_encoder_hidden_states);
     `seperated_word_contexts` is (region table [(token_ids, (r,g,b), strength)], rgb, {ordinal: blurred mask}) (the
@@ -237,17 +265,33 @@ def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, 
     needs from the table + color map, plus the blurred masks of the regions that carry a sigma).
     max_prompt_chunks > 1: a prompt of more than model_max_length - 2 tokens is encoded in up to that many chunks (chunk_prompt), each by
     the text encoder on its own, concatenated along the token axis: CONTEXT_TENSOR [1, 77 k, ctx], weight maps [N, 77 k]. A prompt that needs
-    one chunk takes the code path of the default, whatever the cap. min_prompt_chunks: pad to that many chunks (per-image prompts of a batch)."""
+    one chunk takes the code path of the default, whatever the cap. min_prompt_chunks: pad to that many chunks (per-image prompts of a batch).
+    The chunk count is the larger of what the prompt and the unconditional prompt need under the cap.
+    negative_color_context (extension; the grammar of color_context, read against the same color map, phrases matched in
+    `unconditional_input_prompt`): the unconditional dict then carries weight maps of its own -- a PwWContext with
+    CROSS_ATTENTION_WEIGHT_<N> tensors, a CROSS_ATTENTION_WEIGHT_ORIG built on first access and its own column bound -- which is exactly the
+    dict the reference's builder returns as `cond` when it is called with (negative_color_context, unconditional_input_prompt). None or {}
+    leave the unconditional dict as the reference builds it (the integer 0 in every weight slot). negative_maps=True: all-zero tensors
+    instead of the integers when the context is empty (a batch in which only some requests carry one)."""
     chunk_rows = None
-    if check_prompt_chunks(max_prompt_chunks) > 1 or min_prompt_chunks > 1:
+    if check_prompt_chunks(max_prompt_chunks) > 1:
+        min_prompt_chunks = max(min_prompt_chunks, prompt_chunk_count(tokenizer, unconditional_input_prompt, max_prompt_chunks))
+    if max_prompt_chunks > 1 or min_prompt_chunks > 1:
         content_ids, rows = chunk_prompt(tokenizer, input_prompt, max_prompt_chunks, min_prompt_chunks)
         if len(rows) > 1:
             chunk_rows = rows
     text_input = tokenizer([input_prompt], padding="max_length", max_length=tokenizer.model_max_length,
                            truncation=True, return_tensors="pt")
     color_context, extra_seeds, extra_sigmas = _extract_seed_and_sigma_from_context(color_context)
+    neg_sigmas = {}
+    if negative_color_context:
+        check_negative_context(negative_color_context)
+        if negative_color_context is not color_context:      # (one dict given for both sides: its tails are gone already)
+            negative_color_context, _, neg_sigmas = _extract_seed_and_sigma_from_context(negative_color_context)
+        else:
+            neg_sigmas = dict(extra_sigmas)
     if not use_sigma:      # the pipeline classes parse the sigma tail and drop it (reference :574): no blur there
-        extra_sigmas = {}
+        extra_sigmas, neg_sigmas = {}, {}
     if color_map_image is None:
         # the reference's _image_context_seperator(None, ...) (:239-243): one dummy region over a 512 x 512 all-zero map --
         # plain Stable Diffusion (the pipeline class's default call, `pipe(prompt)`)
@@ -256,6 +300,7 @@ def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, 
         rgb = np.array(color_map_image.convert("RGB")) if hasattr(color_map_image, "convert") else np.asarray(color_map_image)
         height, width = rgb.shape[:2]
         table = _parse_regions(color_context, tokenizer)
+    neg_table = _parse_regions(negative_color_context, tokenizer) if (negative_color_context and rgb is not None) else []
     token_lis = text_input["input_ids"][0].tolist() if chunk_rows is None else [t for row in chunk_rows for t in row]
     from . import attnmaps
     if attnmaps.active() is not None:       # (pww_hip.record_attention_maps: phrase lookup in the recorded maps needs the prompt's tokens)
@@ -268,8 +313,7 @@ def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, 
         blurred = maps.pop("_BLURRED")
         nz_cols = maps.pop("_COLS")
     else:   # empty color_context (:242-243): all-zero maps
-        maps = {k: torch.zeros((k, len(token_lis)), dtype=torch.float32, device=device) for k in keys}
-        maps["ORIG_THUNK"] = lambda: torch.zeros((height, width, len(token_lis)), dtype=torch.float32, device=device)
+        maps = _zero_weight_maps(keys, height, width, len(token_lis), device)
         blurred = {}
         nz_cols = None
 
@@ -278,10 +322,12 @@ def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, 
         uncond_input = tokenizer([unconditional_input_prompt], padding="max_length",
                                  max_length=text_input.input_ids.shape[-1], return_tensors="pt")
         uncond_embeddings = text_encoder(uncond_input.input_ids.to(device))[0]
+        uncond_lis, uncond_content = uncond_input["input_ids"][0].tolist(), None
     else:
         # every chunk through the text encoder on its own (it sees 77 positions, as it was trained), the unconditional prompt to the same k
         k = len(chunk_rows)
-        _, uncond_rows = chunk_prompt(tokenizer, unconditional_input_prompt, k, k)
+        uncond_content, uncond_rows = chunk_prompt(tokenizer, unconditional_input_prompt, k, k)
+        uncond_lis = [t for row in uncond_rows for t in row]
         encode = lambda rows: torch.cat([text_encoder(torch.tensor([row], dtype=torch.long).to(device))[0] for row in rows], dim=1)  # noqa: E731
         cond_embeddings, uncond_embeddings = encode(chunk_rows), encode(uncond_rows)
     if dtype is not None:
@@ -289,10 +335,28 @@ def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, 
 
     # CROSS_ATTENTION_WEIGHT_ORIG (:343-345, :372) is built when somebody indexes it (PwWContext): only inj_forward's KeyError path does
     encoder_hidden_states = PwWContext({"CONTEXT_TENSOR": cond_embeddings}).set_lazy("CROSS_ATTENTION_WEIGHT_ORIG", maps["ORIG_THUNK"])
-    uncond_encoder_hidden_states = {"CONTEXT_TENSOR": uncond_embeddings, "CROSS_ATTENTION_WEIGHT_ORIG": 0}
+    if neg_table or (negative_maps and rgb is not None):
+        # negative regions: one more build_weight_maps per request, over the unconditional prompt's tokens
+        if neg_table:
+            _warn_missing_colors(rgb, neg_table)
+            ncols = None if chunk_rows is None else framed_column_lists(neg_table, uncond_content, len(chunk_rows), tokenizer.model_max_length - 2)
+            nmaps = build_weight_maps(rgb, neg_table, uncond_lis, device, neg_sigmas, cols=ncols)
+            nmaps.pop("_BLURRED")
+            neg_nz = nmaps.pop("_COLS")
+        else:
+            nmaps = _zero_weight_maps(keys, height, width, len(uncond_lis), device)
+            neg_nz = []
+        uncond_encoder_hidden_states = PwWContext({"CONTEXT_TENSOR": uncond_embeddings}).set_lazy("CROSS_ATTENTION_WEIGHT_ORIG", nmaps["ORIG_THUNK"])
+        for k in keys:
+            uncond_encoder_hidden_states[f"CROSS_ATTENTION_WEIGHT_{k}"] = nmaps[k]
+        from .attention import BIAS_COLS
+        uncond_encoder_hidden_states[BIAS_COLS] = ((max(neg_nz) + 16) // 16 * 16) if neg_nz else 16
+    else:
+        uncond_encoder_hidden_states = {"CONTEXT_TENSOR": uncond_embeddings, "CROSS_ATTENTION_WEIGHT_ORIG": 0}
+        for k in keys:
+            uncond_encoder_hidden_states[f"CROSS_ATTENTION_WEIGHT_{k}"] = 0
     for k in keys:
         encoder_hidden_states[f"CROSS_ATTENTION_WEIGHT_{k}"] = maps[k]
-        uncond_encoder_hidden_states[f"CROSS_ATTENTION_WEIGHT_{k}"] = 0
     if nz_cols is not None:
         # Private, optional hints for the fused kernel (SURVEY.md 8b "may add private keys, must not require them"): only the
         # prompt positions covered by a region phrase are non-zero in ANY of the maps (5 - 17 of 77 for the shipped examples) --

@@ -193,8 +193,9 @@ def build_and_broadcast(build_fn, skeleton_fn, device, dtype, src=0, group=None,
 
 def broadcast_request(payload, device, src=0, group=None):
     """Broadcast a request from `src`: every numpy array in the payload dict (the uint8 color map 'rgb', and for
-    inpainting the mask and the init image) travels as a tensor broadcast, everything else (color_context, prompt ...)
-    pickled in one byte tensor. payload on src: dict; None elsewhere. Returns the dict on every rank."""
+    inpainting the mask and the init image) travels as a tensor broadcast, everything else (color_context, prompt, the
+    negative context and its strength ...) pickled in one byte tensor. payload on src: dict; None elsewhere.
+    Returns the dict on every rank."""
     if not (dist.is_available() and dist.is_initialized()):
         return payload
     rank = dist.get_rank()       # global, like `src`

@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from . import attnmaps
-from .attention import install, refresh_kv_cache, refresh_orig_cache, ROW_GATE, KV_CACHE, COEFF_SLOTS, CoeffSlots, COMPACT_W, COMPACT_IDX, GATED_ROWS, ATTN_RECORDER
+from .attention import install, refresh_kv_cache, refresh_orig_cache, ROW_GATE, KV_CACHE, COEFF_SLOTS, CoeffSlots, COMPACT_W, COMPACT_IDX, GATED_ROWS, COND_ROWS, BIAS_COLS, ATTN_RECORDER
 from .conditioning import PwWContext
 
 ORIG = "CROSS_ATTENTION_WEIGHT_ORIG"
@@ -58,11 +58,49 @@ def _as_list(x, n):
     return [x] * n
 
 
-def _fold_context(cond, uncond, n_images, device):
+def _has_negative_maps(d):
+    """Does an unconditional dict carry weight maps of its own (negative regions: conditioning._encode_text_color_inputs with a
+    negative_color_context) instead of the reference's integer 0 in every slot?"""
+    return any(torch.is_tensor(v) for k, v in dict.items(d) if k.startswith("CROSS_ATTENTION_WEIGHT_")) or _orig_pending(d)
+
+
+def _fold_negative(conds, unconds, folded, n_images, negative_strength, device):
+    """The weight entries of a folded dict whose unconditional rows are biased too (negative regions): every map is materialised as
+    [2n, 1, N, T] -- the conditional images' maps, then the unconditional images' -- the gate is [1..., negative_strength...], the column
+    bound is taken over both halves, and no image is gated out: the work-distribution hint is 0 while the recorder still learns that the
+    first n rows are the conditional ones."""
+    folded[ROW_GATE] = torch.cat([torch.ones(n_images), torch.full((n_images,), float(negative_strength))]).to(device=device, dtype=torch.float32)
+    folded[GATED_ROWS] = 0
+    folded[COND_ROWS] = n_images
+    for key in [k for k in list(folded) if k.startswith(COMPACT_W) or k == COMPACT_IDX]:      # (the opt-in compact form is the conditional side's alone)
+        folded.pop(key)
+    if any(_orig_pending(d) or torch.is_tensor(dict.get(d, ORIG)) for d in conds + unconds):
+        def stacked_orig(conds=conds, unconds=unconds):
+            w = [d[ORIG] for d in conds + unconds]
+            if not all(torch.is_tensor(m) for m in w):
+                raise ValueError("negative regions: every context must carry a tensor for %s" % ORIG)
+            return torch.stack(w, dim=0)                         # [2n, H, W, T]
+        folded.pop(ORIG, None)
+        folded.set_lazy(ORIG, stacked_orig)
+    for key in [k for k in dict.keys(conds[0]) if k.startswith("CROSS_ATTENTION_WEIGHT_") and k != ORIG]:
+        maps = [d.get(key) for d in conds + unconds]
+        if not all(torch.is_tensor(m) for m in maps):
+            raise ValueError("negative regions: every context must carry a tensor for %s" % key)
+        if len({tuple(m.shape) for m in maps}) != 1:
+            raise ValueError("negative regions: %s has shapes %s (prompt and unconditional prompt must be encoded to the same number of chunks)"
+                             % (key, sorted({tuple(m.shape) for m in maps})))
+        folded[key] = torch.stack(maps, dim=0).unsqueeze(1)      # [2n, 1, N, T]
+    bounds = [int(d.get(BIAS_COLS, 0) or 0) for d in conds + unconds]
+    folded[BIAS_COLS] = max(bounds) if all(bounds) else 0
+    return folded
+
+
+def _fold_context(cond, uncond, n_images, device, negative_strength=1.0):
     """Build the single dict of a folded call: rows [cond x n, uncond x n]. `cond` / `uncond`: one dict, or one dict per
     image (paint_with_words_batch: per-image prompts and color maps). Per-image weight maps are stacked to
     [2n, 1, N, 77] -- the kernels take the image axis through bias_stride[0] -- with zeros for the unconditional rows
-    (their gate is 0, the values are never used); a shared map stays [N, 77]."""
+    (their gate is 0, the values are never used); a shared map stays [N, 77]. Unconditional dicts with weight maps of their own
+    (negative regions) put those maps into the unconditional rows and `negative_strength` into their gate: _fold_negative."""
     conds, unconds = _as_list(cond, n_images), _as_list(uncond, n_images)
     shared = all(c is conds[0] for c in conds)
 
@@ -78,6 +116,8 @@ def _fold_context(cond, uncond, n_images, device):
     folded["CONTEXT_TENSOR"] = torch.cat([rows(conds), rows(unconds)], dim=0).contiguous()
     folded[ROW_GATE] = torch.cat([torch.ones(n_images), torch.zeros(n_images)]).to(device=device, dtype=torch.float32)
     folded[GATED_ROWS] = n_images        # what the gate holds, for the host side (work distribution of the fused launch)
+    if any(_has_negative_maps(u) for u in unconds):
+        return _fold_negative(conds, unconds, folded, n_images, negative_strength, device)
     if not shared:
         if any(_orig_pending(c) for c in conds):
             # per-image fallback maps, stacked on first use: [2n, H, W, 77] (zeros for the unconditional rows)
@@ -313,8 +353,9 @@ class PwWSampler:
 
     @torch.no_grad()
     def sample(self, cond, uncond, latents, timesteps, guidance_scale, weight_function, extra_channels=None,
-               on_step=None):
+               on_step=None, negative_strength=1.0):
         """cond / uncond: the two context dicts of the PwW protocol, or one dict per image (per-image prompts / maps).
+        An unconditional dict that carries weight maps (negative regions) is evaluated with `negative_strength * weight_function`.
         latents: [n_images, C, h, w] already scaled by init_noise_sigma (or noised for img2img).
         extra_channels: inpaint's cat([mask, masked_image_latents]) ([n or 1, 5, h, w]) or None."""
         sch, unet, dev = self.scheduler, self.unet, latents.device
@@ -329,29 +370,34 @@ class PwWSampler:
         folded = None
         rec = attnmaps.active()        # pww_hip.record_attention_maps(): the recorder rides in the conditional context(s) of this request
         if self.mode != "eager":
-            folded = _fold_context(cond, uncond, n, dev)
+            folded = _fold_context(cond, uncond, n, dev, negative_strength)
             if self._graphed is not None:
                 folded = self._static_context(folded, weight_function, latents, timesteps, rec)
         if extra_channels is not None and extra_channels.shape[0] != n:
             extra_channels = extra_channels.expand(n, -1, -1, -1)
         if rec is None:
-            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, None)
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, None, negative_strength)
         static = self._static_maps if self._graphed is not None else None
         rec.begin_request(n, latents.shape[-2:], static=static)      # (hipGraph mode: zeroes the static accumulators, before the first replay)
         holders = conds if folded is None else [folded]
         for d in holders:
             d[ATTN_RECORDER] = rec
         try:
-            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec)
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength)
         finally:
             for d in holders:
                 d.pop(ATTN_RECORDER, None)
             rec.end_request(static=static is not None)
 
-    def _denoise(self, conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec):
+    def _denoise(self, conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength=1.0):
         """The loop of sample() (reference :470-506)."""
         sch, unet, n = self.scheduler, self.unet, latents.shape[0]
         udt = unet.dtype if hasattr(unet, "dtype") else next(unet.parameters()).dtype
+        zero_function = lambda w, sigma, qk: 0.0      # noqa: E731  (the reference's unconditional pass, :493)
+        ns = float(negative_strength)
+        negative_function = lambda w, sigma, qk: ns * weight_function(w, sigma, qk)      # noqa: E731
+        # eager mode: per image, what its unconditional dict is evaluated with (one with weight maps of its own: negative regions)
+        uncond_functions = [negative_function if _has_negative_maps(u) else zero_function for u in unconds] if folded is None else None
         for i, t in enumerate(timesteps):
             sigma, _ = self._sigma_and_index(i, t)
             x = sch.scale_model_input(latents, t)
@@ -364,7 +410,7 @@ class PwWSampler:
                     if rec is not None:
                         rec.row = j
                     eps_c.append(unet(x[j:j + 1], t, encoder_hidden_states=conds[j]).sample)
-                    unconds[j].update({"SIGMA": sigma, "WEIGHT_FUNCTION": lambda w, sigma, qk: 0.0})
+                    unconds[j].update({"SIGMA": sigma, "WEIGHT_FUNCTION": uncond_functions[j]})
                     eps_u.append(unet(x[j:j + 1], t, encoder_hidden_states=unconds[j]).sample)
                 eps_c, eps_u = torch.cat(eps_c), torch.cat(eps_u)
             else:
