@@ -12,6 +12,7 @@ samples by a sequential loop over seeds that reloads the model each time, gradio
 """
 import math
 import os
+from functools import partial
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -44,10 +45,13 @@ def preprocess(image):
     return 2.0 * torch.from_numpy(pixels[None].transpose(0, 3, 1, 2)) - 1.0
 
 
-def _pil_from_latents(vae, latents):
-    """reference :48-57: decode the latents, one PIL image per batch row."""
+def _pil_from_latents(vae, latents, output_type="pil"):
+    """reference :48-57: decode the latents, one PIL image per batch row -- or, for the pipeline classes' other output types, the
+    [n, H, W, 3] float array of the diffusers pipeline's decode_latents (:821-833)."""
     decoded = vae.decode((latents.clone() / 0.18215).to(vae.dtype)).sample
     pixels = (decoded / 2 + 0.5).clamp(0, 1).detach().float().cpu().permute(0, 2, 3, 1).numpy()
+    if output_type != "pil":
+        return pixels
     return [Image.fromarray(im) for im in (pixels * 255).round().astype("uint8")]
 
 
@@ -81,16 +85,24 @@ def pww_load_tools(device: str = "cuda:0", scheduler_type=LMSDiscreteScheduler, 
     return vae, unet, text_encoder, tokenizer, scheduler
 
 
+def _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token):
+    """(vae, unet, text_encoder, tokenizer, scheduler): the caller's `preloaded_utils`, or loaded as the reference does."""
+    if preloaded_utils is not None:
+        return preloaded_utils
+    return pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path, model_token=model_token)
+
+
 def _unet_dtype(unet):
     return unet.dtype if hasattr(unet, "dtype") else next(unet.parameters()).dtype
 
 
-def _sampler_for(unet, scheduler, mode):
-    """One PwWSampler (and its captured graphs) per (unet, scheduler, mode), kept on the unet."""
+def _sampler_for(unet, scheduler):
+    """One PwWSampler (and its captured graphs) per (unet, scheduler, mode), kept on the unet. The mode is DEFAULT_MODE as it is NOW: every
+    face of the package finds its sampler here, so assigning this module's global takes effect everywhere."""
     cache = unet.__dict__.setdefault("_pww_samplers", {})
-    key = (id(scheduler), mode)
+    key = (id(scheduler), DEFAULT_MODE)
     if key not in cache:
-        cache[key] = PwWSampler(unet, scheduler, mode)
+        cache[key] = PwWSampler(unet, scheduler, DEFAULT_MODE)
     return cache[key]
 
 
@@ -118,22 +130,72 @@ def _negative_contexts(negative_color_contexts, n, color_map_images):
     return negs, any(c is not None for c in negs)
 
 
-def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale,
-              weight_function, unconditional_input_prompt, init_images=None, strength=0.5, latent_hw=None,
-              on_step=None, use_region_sigma=True, shared=False, max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0):
-    """Shared body of paint_with_words / paint_with_words_batch / the pipeline class (reference :414-506): conditioning
-    per request (once if every request shares map, context and prompt), CPU-generated latents per seed exactly as :446,
-    one denoise loop over all images. Returns the final latents [n, 4, h, w]. negative_color_contexts: None, or one dict (or None) per
-    request like color_contexts -- regions of the unconditional prompt (see paint_with_words)."""
-    vae, unet, text_encoder, tokenizer, scheduler = tools
+def _batch_requests(n, color_contexts, negative_color_context, color_map_images, input_prompts, strip_color_contexts):
+    """The per-request arguments a batch function shares with its twin -> (color contexts, negative contexts, color maps, prompts: n of
+    each; `shared`: every request has the same four, so one conditioning serves all; the caller's dicts to strip after the call). Not
+    shared: one dict may serve several requests, so a private copy per request is parsed and the caller's dicts -- the negative ones, and
+    the color contexts if `strip_color_contexts` -- lose their tails afterwards, each object once."""
+    ctxs, s1 = _broadcast(color_contexts, n, "color_context")
+    negs, s4 = _broadcast(negative_color_context, n, "negative_color_context")
+    maps, s2 = _broadcast(color_map_images, n, "color_map_images")
+    prompts, s3 = _broadcast(input_prompts, n, "input_prompts")
+    if s1 and s2 and s3 and s4:
+        return ctxs, negs, maps, prompts, True, []
+    strip = {id(c): c for c in (ctxs if strip_color_contexts else []) + [c for c in negs if c]}
+    return [dict(c) for c in ctxs], [dict(c) if c else None for c in negs], maps, prompts, False, list(strip.values())
+
+
+def _seeded_noise(tools, device, seeds, timesteps, seeds_info, sizes):
+    """txt2img (:444-457): CPU-generated latents per seed exactly as :446, with the region seeds; `sizes`: (width, height) per request."""
+    unet, scheduler = tools[1], tools[4]
+    lats = [initial_latents(seed, unet.in_channels, height, width, extra_seeds=extra_seeds,
+                            region_masks=lambda dtype, size, ri=region_info, es=extra_seeds: _get_binary_mask(ri, es, dtype, size))
+            for seed, (width, height), (extra_seeds, region_info) in zip(seeds, sizes, seeds_info)]
+    return torch.cat(lats, dim=0).to(device) * scheduler.init_noise_sigma, None
+
+
+def _noised_images(tools, device, seeds, timesteps, seeds_info, init_images):
+    """img2img (:459-468): the init images through the VAE encoder, noised to the first timestep (noise from the global generator)."""
+    vae, scheduler = tools[0], tools[4]
+    lats = []
+    for init_image in init_images:
+        image = preprocess(init_image).to(device=device)
+        init_latents = 0.18215 * vae.encode(image.to(vae.dtype)).latent_dist.sample().float()
+        noise = torch.randn(init_latents.shape).to(device)
+        lats.append(scheduler.add_noise(init_latents, noise, timesteps[:1]))
+    return torch.cat(lats, dim=0), None
+
+
+def _txt2img_or_img2img(sizes, init_images, strength):
+    """-> the (`start`, `strength`) arguments of _generate for a face that takes optional init images."""
+    if init_images is None:
+        return partial(_seeded_noise, sizes=sizes), None
+    return partial(_noised_images, init_images=init_images), strength
+
+
+def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
+              unconditional_input_prompt, start, strength=None, map_sizes=None, on_step=None, use_region_sigma=True, shared=False,
+              max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0):
+    """The body behind every face of the package (reference :414-506, paint_with_words_inpaint.py:160-262): conditioning per request (once
+    if `shared`: every request has the same map, context and prompt), the timesteps, the initial state, one denoise loop over all images.
+    Returns the final latents [n, 4, h, w].
+    start(tools, device, seeds, timesteps, seeds_info) -> (latents [n, 4, h, w], extra UNet input channels [n, 5, h, w] or None) is the
+    initial state: _seeded_noise, _noised_images or the inpaint module's _inpaint_start. strength: None runs every timestep (txt2img), a
+    number the img2img tail of the schedule (:434-441). map_sizes: one (width, height) per request to resize its color map to (the inpaint
+    function API, paint_with_words_inpaint.py:172). negative_color_contexts: None, or one dict (or None) per request like color_contexts --
+    regions of the unconditional prompt (see paint_with_words)."""
+    unet, text_encoder, tokenizer, scheduler = tools[1:]
     n = len(seeds)
-    sampler = _sampler_for(unet, scheduler, DEFAULT_MODE)   # also installs the attention plug
+    sampler = _sampler_for(unet, scheduler)   # also installs the attention plug
     conds, unconds, seeds_info = [], [], []
     min_chunks = _batch_prompt_chunks(tokenizer, (prompts[:1] if shared else prompts) + [unconditional_input_prompt], max_prompt_chunks)
     negs, any_neg = _negative_contexts(negative_color_contexts, n, color_map_images)
     for i in range(1 if shared else n):
+        color_map = color_map_images[i]
+        if map_sizes is not None and color_map is not None:
+            color_map = color_map.resize(map_sizes[i], Image.NEAREST)
         extra_seeds, region_info, cond, uncond = _encode_text_color_inputs(
-            text_encoder, tokenizer, device, color_map_images[i], color_contexts[i], prompts[i], unconditional_input_prompt,
+            text_encoder, tokenizer, device, color_map, color_contexts[i], prompts[i], unconditional_input_prompt,
             dtype=_unet_dtype(unet), use_sigma=use_region_sigma, max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks,
             negative_color_context=negs[i], negative_maps=any_neg)
         conds.append(cond), unconds.append(uncond), seeds_info.append((extra_seeds, region_info))
@@ -141,32 +203,28 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
         conds, unconds, seeds_info = conds[0], unconds[0], seeds_info * n
 
     scheduler.set_timesteps(num_inference_steps)
-    if init_images is None:          # txt2img, :444-457
-        timesteps = scheduler.timesteps
-        lats = []
-        for i in range(n):
-            width, height = color_map_images[i].size if latent_hw is None else (latent_hw[1], latent_hw[0])
-            extra_seeds, region_info = seeds_info[i]
-            lats.append(initial_latents(seeds[i], unet.in_channels, height, width,
-                                        region_masks=lambda dtype, size, ri=region_info, es=extra_seeds: _get_binary_mask(ri, es, dtype, size),
-                                        extra_seeds=extra_seeds))
-        latents = torch.cat(lats, dim=0).to(device) * scheduler.init_noise_sigma
-    else:                            # img2img, :434-441, :459-468
+    timesteps = scheduler.timesteps
+    if strength is not None:
         offset = scheduler.config.get("steps_offset", 0)
         init_timestep = min(int(num_inference_steps * strength) + offset, num_inference_steps)
-        t_start = max(num_inference_steps - init_timestep + offset, 0)
-        timesteps = scheduler.timesteps[t_start:]
-        lats = []
-        for i in range(n):
-            image = preprocess(init_images[i]).to(device=device)
-            init_latents = 0.18215 * vae.encode(image.to(vae.dtype)).latent_dist.sample().float()
-            noise = torch.randn(init_latents.shape).to(device)
-            lats.append(scheduler.add_noise(init_latents, noise, timesteps[:1]))
-        latents = torch.cat(lats, dim=0)
+        timesteps = timesteps[max(num_inference_steps - init_timestep + offset, 0):]
 
+    latents, extra_channels = start(tools, device, seeds, timesteps, seeds_info)
     with pww_hip.miopen_find():
-        return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, on_step=on_step,
-                              negative_strength=negative_strength)
+        return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra_channels,
+                              on_step=on_step, negative_strength=negative_strength)
+
+
+def _finish(tools, latents, return_latents=False, decode=None):
+    """What a face returns for the final latents: the latents themselves (`return_latents`), or the decoded images -- a list of PIL images,
+    or what the pipeline classes' `decode` makes of _pil_from_latents. Either way a fused hand-off that timed out raises here instead of
+    handing back NaNs."""
+    sampler = _sampler_for(tools[1], tools[4])
+    if return_latents:
+        return sampler.checked(latents)
+    images = (decode or _pil_from_latents)(tools[0], latents)
+    sampler.check_errors()     # (the decode above synchronised already)
+    return images
 
 
 @torch.no_grad()
@@ -204,17 +262,13 @@ def paint_with_words(
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     color_map_image.size     # the reference dereferences it unconditionally (:414): None raises here too
-    tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
-                            model_token=model_token) if preloaded_utils is None else preloaded_utils)
-    latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps,
-                        guidance_scale, weight_function, unconditional_input_prompt,
-                        init_images=None if init_image is None else [init_image], strength=strength, shared=True,
-                        max_prompt_chunks=max_prompt_chunks, negative_color_contexts=[negative_color_context], negative_strength=negative_strength)
-    if return_latents:
-        return _sampler_for(tools[1], tools[4], DEFAULT_MODE).checked(latents)
-    image = _pil_from_latents(tools[0], latents)[0]
-    _sampler_for(tools[1], tools[4], DEFAULT_MODE).check_errors()     # (the decode above synchronised already)
-    return image
+    tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
+    start, strength = _txt2img_or_img2img([color_map_image.size], None if init_image is None else [init_image], strength)
+    latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps, guidance_scale,
+                        weight_function, unconditional_input_prompt, start, strength, shared=True, max_prompt_chunks=max_prompt_chunks,
+                        negative_color_contexts=[negative_color_context], negative_strength=negative_strength)
+    out = _finish(tools, latents, return_latents)
+    return out if return_latents else out[0]
 
 
 @torch.no_grad()
@@ -256,32 +310,20 @@ def paint_with_words_batch(
     n = len(seeds)
     if n == 0:
         return []
-    ctxs, s1 = _broadcast(color_contexts, n, "color_context")
-    negs, s4 = _broadcast(negative_color_context, n, "negative_color_context")
-    maps, s2 = _broadcast(color_map_images, n, "color_map_images")
-    prompts, s3 = _broadcast(input_prompts, n, "input_prompts")
+    ctxs, negs, maps, prompts, shared, strip = _batch_requests(n, color_contexts, negative_color_context, color_map_images, input_prompts,
+                                                               strip_color_contexts=True)
     inits = None if init_images is None else _broadcast(init_images, n, "init_images")[0]
     if len({m.size for m in maps}) != 1:
         raise ValueError("paint_with_words_batch: all color maps of one call must have the same size, got %s"
                          % sorted({m.size for m in maps}))
-    shared = s1 and s2 and s3 and s4
-    originals = ctxs + [c for c in negs if c]
-    if not shared:       # one dict may serve several requests: parse a private copy per request, strip the caller's afterwards
-        ctxs = [dict(c) for c in ctxs]
-        negs = [dict(c) if c else None for c in negs]
-    tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
-                            model_token=model_token) if preloaded_utils is None else preloaded_utils)
+    tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
+    start, strength = _txt2img_or_img2img([m.size for m in maps], inits, strength)
     latents = _generate(tools, device, ctxs, maps, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
-                        unconditional_input_prompt, init_images=inits, strength=strength, shared=shared, max_prompt_chunks=max_prompt_chunks,
+                        unconditional_input_prompt, start, strength, shared=shared, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=negs, negative_strength=negative_strength)
-    if not shared:
-        for c in {id(c): c for c in originals}.values():
-            _extract_seed_and_sigma_from_context(c)
-    if return_latents:
-        return _sampler_for(tools[1], tools[4], DEFAULT_MODE).checked(latents)
-    images = _pil_from_latents(tools[0], latents)
-    _sampler_for(tools[1], tools[4], DEFAULT_MODE).check_errors()
-    return images
+    for c in strip:
+        _extract_seed_and_sigma_from_context(c)
+    return _finish(tools, latents, return_latents)
 
 
 def __getattr__(name):

@@ -3,6 +3,7 @@ the inpainting variant feeds a 9-channel UNet input cat([latents, mask, masked_i
 (reference :237, :250); the attention path is the same fused HIP op, and the mask / masked-image
 preparation (reference :20-134) is one HIP kernel (pww_inpaint_prep) over the uint8 pixels."""
 import math
+from functools import partial
 from typing import Callable, Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -10,18 +11,9 @@ import torch
 import torch.nn.functional as F
 from PIL import Image
 
-import pww_hip
 from pww_hip import ops
-_pw_module_name = __name__.rsplit(".", 1)[0] + ".paint_with_words"      # the function-API module: its DEFAULT_MODE is read at call time
-from .paint_with_words import (LMSDiscreteScheduler, pww_load_tools, preprocess, _pil_from_latents,
-                               _encode_text_color_inputs, _sampler_for, _unet_dtype, _broadcast, _batch_prompt_chunks,
-                               check_prompt_chunks, check_negative_context, _negative_contexts,
-                               _extract_seed_and_sigma_from_context)
-
-
-def _mode():
-    import sys
-    return sys.modules[_pw_module_name].DEFAULT_MODE
+from .paint_with_words import (LMSDiscreteScheduler, _tools, _generate, _finish, _broadcast, _batch_requests, check_prompt_chunks,
+                               check_negative_context, preprocess, _extract_seed_and_sigma_from_context)
 
 
 def _as_uint8_pixels(image, channels):
@@ -115,47 +107,20 @@ def _inpaint_inputs(vae, init_image, mask_image, seed, scheduler, timesteps, dev
     return latents, torch.cat([mask_lat.to(latents.dtype), masked_latents], dim=1)
 
 
-def _generate_inpaint(tools, device, color_contexts, color_map_images, mask_images, init_images, prompts, seeds,
-                      num_inference_steps, guidance_scale, weight_function, unconditional_input_prompt, strength, shared,
-                      on_step=None, mask_hw=None, resize_inputs=True, use_region_sigma=True, max_prompt_chunks=1,
-                      negative_color_contexts=None, negative_strength=1.0):
-    """Shared body of paint_with_words_inpaint / _batch / the inpaint pipeline class. The function API resizes color map and
-    mask to the init image (:172-173, `resize_inputs`); the pipeline class does not and sizes the latent mask by `mask_hw`."""
-    vae, unet, text_encoder, tokenizer, scheduler = tools
-    n = len(seeds)
-    sampler = _sampler_for(unet, scheduler, _mode())
-    conds, unconds = [], []
-    min_chunks = _batch_prompt_chunks(tokenizer, (prompts[:1] if shared else prompts) + [unconditional_input_prompt], max_prompt_chunks)
-    negs, any_neg = _negative_contexts(negative_color_contexts, n, color_map_images)
-    for i in range(1 if shared else n):
-        width, height = init_images[i].size
-        color_map = color_map_images[i]
-        if resize_inputs and color_map is not None:
-            color_map = color_map.resize((width, height), Image.NEAREST)            # :172
-        _, _, cond, uncond = _encode_text_color_inputs(text_encoder, tokenizer, device, color_map, color_contexts[i], prompts[i],
-                                                       unconditional_input_prompt, dtype=_unet_dtype(unet), use_sigma=use_region_sigma,
-                                                       max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks,
-                                                       negative_color_context=negs[i], negative_maps=any_neg)
-        conds.append(cond), unconds.append(uncond)
-    if shared:
-        conds, unconds = conds[0], unconds[0]
-
-    scheduler.set_timesteps(num_inference_steps)
-    offset = scheduler.config.get("steps_offset", 0)
-    init_timestep = min(int(num_inference_steps * strength) + offset, num_inference_steps)
-    t_start = max(num_inference_steps - init_timestep + offset, 0)
-    timesteps = scheduler.timesteps[t_start:]
-
+def _inpaint_start(tools, device, seeds, timesteps, seeds_info, init_images, mask_images, mask_hw=None, resize_inputs=True):
+    """The initial state of an inpainting request for _generate: noised init-image latents plus cat([mask, masked-image latents]) for the
+    9-channel UNet. The function API resizes the mask to the init image (:173, `resize_inputs`); the pipeline class does not and sizes the
+    latent mask by `mask_hw`."""
+    vae, unet, scheduler = tools[0], tools[1], tools[4]
     lats, extras = [], []
-    for i in range(n):
-        width, height = init_images[i].size
-        mask_image = mask_images[i].resize((width, height), Image.NEAREST) if resize_inputs else mask_images[i]      # :173
-        if mask_image.size != init_images[i].size:
+    for init_image, mask_image, seed in zip(init_images, mask_images, seeds):
+        if resize_inputs:
+            mask_image = mask_image.resize(init_image.size, Image.NEAREST)
+        if mask_image.size != init_image.size:
             raise AssertionError("Image and Mask must have the same spatial dimensions")                            # :72-73
-        lat, extra = _inpaint_inputs(vae, init_images[i], mask_image, seeds[i], scheduler, timesteps, device, mask_hw=mask_hw)
+        lat, extra = _inpaint_inputs(vae, init_image, mask_image, seed, scheduler, timesteps, device, mask_hw=mask_hw)
         lats.append(lat), extras.append(extra)
     latents, extra = torch.cat(lats, dim=0), torch.cat(extras, dim=0)
-
     n_lat, n_extra = latents.shape[1], extra.shape[1]
     if n_lat + n_extra != unet.in_channels:
         config = getattr(unet, "config", None)
@@ -163,9 +128,7 @@ def _generate_inpaint(tools, device, color_contexts, color_map_images, mask_imag
             f"Incorrect configuration settings! The config of `pipeline.unet`: {config} expects {unet.in_channels} input "
             f"channels but received {n_lat} latent + 1 mask + {n_extra - 1} masked-image latent channels = {n_lat + n_extra}. "
             "Please verify the config of `pipeline.unet` or your `mask_image` or `image` input.")
-    with pww_hip.miopen_find():
-        return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra, on_step=on_step,
-                              negative_strength=negative_strength)
+    return latents, extra
 
 
 @torch.no_grad()
@@ -195,17 +158,13 @@ def paint_with_words_inpaint(
     """reference :137-270. negative_color_context / negative_strength / max_prompt_chunks (extensions): see paint_with_words."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
-    tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
-                            model_token=model_token) if preloaded_utils is None else preloaded_utils)
-    latents = _generate_inpaint(tools, device, [color_context], [color_map_image], [mask_image], [init_image], [input_prompt],
-                                [seed], num_inference_steps, guidance_scale, weight_function, unconditional_input_prompt,
-                                strength, shared=True, max_prompt_chunks=max_prompt_chunks,
-                                negative_color_contexts=[negative_color_context], negative_strength=negative_strength)
-    if return_latents:
-        return _sampler_for(tools[1], tools[4], _mode()).checked(latents)
-    image = _pil_from_latents(tools[0], latents)[0]
-    _sampler_for(tools[1], tools[4], _mode()).check_errors()
-    return image
+    tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
+    latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps, guidance_scale,
+                        weight_function, unconditional_input_prompt, partial(_inpaint_start, init_images=[init_image], mask_images=[mask_image]),
+                        strength, map_sizes=[init_image.size], shared=True, max_prompt_chunks=max_prompt_chunks,
+                        negative_color_contexts=[negative_color_context], negative_strength=negative_strength)
+    out = _finish(tools, latents, return_latents)
+    return out if return_latents else out[0]
 
 
 @torch.no_grad()
@@ -242,31 +201,21 @@ def paint_with_words_inpaint_batch(
     n = len(seeds)
     if n == 0:
         return []
-    ctxs, s1 = _broadcast(color_contexts, n, "color_context")
-    maps, s2 = _broadcast(color_map_images, n, "color_map_images")
+    # (private copies are parsed when the requests differ; this function strips the caller's negative dicts only afterwards)
+    ctxs, negs, maps, prompts, shared, strip = _batch_requests(n, color_contexts, negative_color_context, color_map_images, input_prompts,
+                                                               strip_color_contexts=False)
     masks, _ = _broadcast(mask_images, n, "mask_images")
     inits, _ = _broadcast(init_images, n, "init_images")
-    prompts, s3 = _broadcast(input_prompts, n, "input_prompts")
     if len({im.size for im in inits}) != 1:
         raise ValueError("paint_with_words_inpaint_batch: all init images of one call must have the same size")
-    negs, s4 = _broadcast(negative_color_context, n, "negative_color_context")
-    originals = [c for c in negs if c]
-    if not (s1 and s2 and s3 and s4):
-        ctxs = [dict(c) for c in ctxs]
-        negs = [dict(c) if c else None for c in negs]
-    tools = (pww_load_tools(device, scheduler_type, local_model_path=local_model_path, hf_model_path=hf_model_path,
-                            model_token=model_token) if preloaded_utils is None else preloaded_utils)
-    latents = _generate_inpaint(tools, device, ctxs, maps, masks, inits, prompts, seeds, num_inference_steps, guidance_scale,
-                                weight_function, unconditional_input_prompt, strength, shared=s1 and s2 and s3 and s4,
-                                max_prompt_chunks=max_prompt_chunks, negative_color_contexts=negs, negative_strength=negative_strength)
-    if not (s1 and s2 and s3 and s4):      # (private copies were parsed: strip the caller's negative dicts, as the single-request call does)
-        for c in {id(c): c for c in originals}.values():
-            _extract_seed_and_sigma_from_context(c)
-    if return_latents:
-        return _sampler_for(tools[1], tools[4], _mode()).checked(latents)
-    images = _pil_from_latents(tools[0], latents)
-    _sampler_for(tools[1], tools[4], _mode()).check_errors()
-    return images
+    tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
+    latents = _generate(tools, device, ctxs, maps, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
+                        unconditional_input_prompt, partial(_inpaint_start, init_images=inits, mask_images=masks), strength,
+                        map_sizes=[im.size for im in inits], shared=shared, max_prompt_chunks=max_prompt_chunks,
+                        negative_color_contexts=negs, negative_strength=negative_strength)
+    for c in strip:
+        _extract_seed_and_sigma_from_context(c)
+    return _finish(tools, latents, return_latents)
 
 
 def __getattr__(name):

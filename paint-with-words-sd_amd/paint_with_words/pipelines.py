@@ -16,19 +16,17 @@ Behaviour the reference's pipeline variant has and the function API has not, kep
 """
 import math
 import warnings
+from functools import partial
 from types import SimpleNamespace
 from typing import Callable, Dict, List, Optional, Tuple, Union
 
-import numpy as np
 import torch
 from PIL import Image
 
 import pww_hip
-import importlib
-_pw = importlib.import_module(__name__.rsplit(".", 1)[0] + ".paint_with_words")
-from .paint_with_words import (pww_load_tools, LMSDiscreteScheduler, _generate, _pil_from_latents, _sampler_for, check_prompt_chunks,
+from .paint_with_words import (LMSDiscreteScheduler, _generate, _finish, _pil_from_latents, _txt2img_or_img2img, check_prompt_chunks,
                                check_negative_context)
-from . import paint_with_words_inpaint as _inp
+from .paint_with_words_inpaint import _inpaint_start
 
 _warned = set()
 
@@ -40,12 +38,8 @@ def _unused(name, value, default):
 
 
 def _decode(vae, latents, output_type):
-    """decode_latents + numpy_to_pil of the diffusers pipeline (:821-833): [n, H, W, 3] float array or PIL images."""
-    decoded = vae.decode((latents / 0.18215).to(vae.dtype)).sample
-    pixels = (decoded / 2 + 0.5).clamp(0, 1).float().cpu().permute(0, 2, 3, 1).numpy()
-    if output_type == "pil":
-        return [Image.fromarray(im) for im in (pixels * 255).round().astype("uint8")]
-    return pixels
+    """decode_latents + numpy_to_pil of the diffusers pipeline (:821-833), by the package's one decoder: [n, H, W, 3] float array or PIL images."""
+    return _pil_from_latents(vae, latents, output_type)
 
 
 class PaintWithWord_StableDiffusionPipeline:
@@ -93,20 +87,47 @@ class PaintWithWord_StableDiffusionPipeline:
         if pww_hip.install(self.unet) == 0 and hasattr(self.unet, "set_attn_processor"):
             self.unet.set_attn_processor(pww_hip.PwWAttnProcessor())
 
-    def _tools(self):
-        return (self.vae, self.unet, self.text_encoder, self.tokenizer, self.scheduler)
-
     def _default_side(self):
         cfg = getattr(self.unet, "config", None)
         size = cfg.get("sample_size") if isinstance(cfg, dict) else getattr(cfg, "sample_size", None)
         return (size or 64) * self.vae_scale_factor
 
-    @staticmethod
-    def _callback_adapter(callback, callback_steps):
-        """the reference calls `callback(i, t, latents)` every `callback_steps` steps (:815-816)"""
-        if callback is None:
-            return None
-        return lambda i, t, latents: callback(i, t, latents) if i % callback_steps == 0 else None
+    def _check_extensions(self):
+        check_prompt_chunks(self.max_prompt_chunks)
+        check_negative_context(self.negative_color_context, self.negative_strength)
+
+    def _check_inputs(self, prompt, height, width, negative_prompt, num_images_per_prompt, generator, latents, callback_steps):
+        """The argument block both __call__s share (check_inputs of the diffusers base class, :431) -> (prompt, height, width,
+        negative_prompt) as the generation body takes them."""
+        height = height or self._default_side()                      # :427-428
+        width = width or self._default_side()
+        if height % 8 or width % 8:
+            raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
+        if callback_steps is None or not isinstance(callback_steps, int) or callback_steps <= 0:
+            raise ValueError(f"`callback_steps` has to be a positive integer but is {callback_steps} of type {type(callback_steps)}.")
+        if not isinstance(prompt, str):
+            if not isinstance(prompt, (list, tuple)) or len(prompt) != 1:
+                raise ValueError("`prompt` has to be a str (the reference's pipeline generates one image per call)")
+            prompt = prompt[0]
+        if isinstance(negative_prompt, (list, tuple)):
+            negative_prompt = negative_prompt[0] if negative_prompt else ""
+        _unused("num_images_per_prompt", num_images_per_prompt, 1)
+        _unused("generator", generator, None)
+        _unused("latents", latents, None)
+        return prompt, height, width, negative_prompt or ""
+
+    def _run(self, start, strength, prompt, color_map_image, color_context, weight_function, num_inference_steps, guidance_scale,
+             negative_prompt, seed, output_type, return_dict, callback, callback_steps):
+        """One request through the generation body of the function API, returned as the diffusers pipeline returns it (:821-842). The
+        reference calls `callback(i, t, latents)` every `callback_steps` steps (:815-816)."""
+        on_step = None if callback is None else (lambda i, t, latents: callback(i, t, latents) if i % callback_steps == 0 else None)
+        tools = (self.vae, self.unet, self.text_encoder, self.tokenizer, self.scheduler)
+        lat = _generate(tools, str(self.device), [color_context], [color_map_image], [prompt], [seed], num_inference_steps, guidance_scale,
+                        weight_function, negative_prompt, start, strength, on_step=on_step, use_region_sigma=False, shared=True,
+                        max_prompt_chunks=self.max_prompt_chunks, negative_color_contexts=[self.negative_color_context],
+                        negative_strength=self.negative_strength)
+        images = _finish(tools, lat, decode=lambda vae, latents: _decode(vae, latents, output_type))
+        return SimpleNamespace(images=images, nsfw_content_detected=False) if return_dict else (images, False)
 
     @torch.no_grad()
     def __call__(
@@ -132,34 +153,12 @@ class PaintWithWord_StableDiffusionPipeline:
         callback_steps: Optional[int] = 1,
     ):
         """reference :629-842 (same parameter list, order and defaults). Prompts longer than 75 tokens: `self.max_prompt_chunks`."""
-        max_prompt_chunks = check_prompt_chunks(self.max_prompt_chunks)
-        check_negative_context(self.negative_color_context, self.negative_strength)
-        height = height or self._default_side()
-        width = width or self._default_side()
-        if height % 8 or width % 8:                                   # check_inputs of the diffusers base class
-            raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
-        if callback_steps is None or not isinstance(callback_steps, int) or callback_steps <= 0:
-            raise ValueError(f"`callback_steps` has to be a positive integer but is {callback_steps} of type {type(callback_steps)}.")
-        if not isinstance(prompt, str):
-            if not isinstance(prompt, (list, tuple)) or len(prompt) != 1:
-                raise ValueError("`prompt` has to be a str (the reference's pipeline generates one image per call)")
-            prompt = prompt[0]
-        if isinstance(negative_prompt, (list, tuple)):
-            negative_prompt = negative_prompt[0] if negative_prompt else ""
-        _unused("num_images_per_prompt", num_images_per_prompt, 1)
-        _unused("generator", generator, None)
-        _unused("latents", latents, None)
-
-        lat = _generate(self._tools(), str(self.device), [color_context], [color_map_image], [prompt], [seed], num_inference_steps,
-                        guidance_scale, weight_function, negative_prompt or "", init_images=None if image is None else [image],
-                        strength=eta, latent_hw=(height, width), use_region_sigma=False, shared=True,
-                        on_step=self._callback_adapter(callback, callback_steps), max_prompt_chunks=max_prompt_chunks,
-                        negative_color_contexts=[self.negative_color_context], negative_strength=self.negative_strength)
-        images = _decode(self.vae, lat, output_type)
-        _sampler_for(self.unet, self.scheduler, _pw.DEFAULT_MODE).check_errors()
-        if not return_dict:
-            return (images, False)
-        return SimpleNamespace(images=images, nsfw_content_detected=False)
+        self._check_extensions()
+        prompt, height, width, negative_prompt = self._check_inputs(prompt, height, width, negative_prompt, num_images_per_prompt, generator,
+                                                                    latents, callback_steps)
+        start, strength = _txt2img_or_img2img([(width, height)], None if image is None else [image], eta)
+        return self._run(start, strength, prompt, color_map_image, color_context, weight_function, num_inference_steps, guidance_scale,
+                         negative_prompt, seed, output_type, return_dict, callback, callback_steps)
 
 
 class PaintWithWord_StableDiffusionInpaintPipeline(PaintWithWord_StableDiffusionPipeline):
@@ -189,31 +188,11 @@ class PaintWithWord_StableDiffusionInpaintPipeline(PaintWithWord_StableDiffusion
     ):
         """reference paint_with_words_inpaint.py:340-575 (same parameter list, order and defaults). Prompts longer than 75 tokens:
         `self.max_prompt_chunks`."""
-        max_prompt_chunks = check_prompt_chunks(self.max_prompt_chunks)
-        check_negative_context(self.negative_color_context, self.negative_strength)
+        self._check_extensions()
         if image is None or mask_image is None:
             raise ValueError("`image` and `mask_image` are required for inpainting")
-        height = height or self._default_side()                      # :427-428
-        width = width or self._default_side()
-        if height % 8 or width % 8:                                   # check_inputs of the diffusers base class (:431)
-            raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
-        if callback_steps is None or not isinstance(callback_steps, int) or callback_steps <= 0:
-            raise ValueError(f"`callback_steps` has to be a positive integer but is {callback_steps} of type {type(callback_steps)}.")
-        if not isinstance(prompt, str):
-            if not isinstance(prompt, (list, tuple)) or len(prompt) != 1:
-                raise ValueError("`prompt` has to be a str (the reference's pipeline generates one image per call)")
-            prompt = prompt[0]
-        if isinstance(negative_prompt, (list, tuple)):
-            negative_prompt = negative_prompt[0] if negative_prompt else ""
-        for name, value, default in (("num_images_per_prompt", num_images_per_prompt, 1), ("generator", generator, None), ("latents", latents, None)):
-            _unused(name, value, default)
-        lat = _inp._generate_inpaint(self._tools(), str(self.device), [color_context], [color_map_image], [mask_image], [image], [prompt],
-                                     [seed], num_inference_steps, guidance_scale, weight_function, negative_prompt or "", eta, shared=True,
-                                     on_step=self._callback_adapter(callback, callback_steps), mask_hw=(height, width), resize_inputs=False,
-                                     use_region_sigma=False, max_prompt_chunks=max_prompt_chunks,
-                                     negative_color_contexts=[self.negative_color_context], negative_strength=self.negative_strength)
-        images = _decode(self.vae, lat, output_type)
-        _sampler_for(self.unet, self.scheduler, _pw.DEFAULT_MODE).check_errors()
-        if not return_dict:
-            return (images, False)
-        return SimpleNamespace(images=images, nsfw_content_detected=False)
+        prompt, height, width, negative_prompt = self._check_inputs(prompt, height, width, negative_prompt, num_images_per_prompt, generator,
+                                                                    latents, callback_steps)
+        start = partial(_inpaint_start, init_images=[image], mask_images=[mask_image], mask_hw=(height, width), resize_inputs=False)
+        return self._run(start, eta, prompt, color_map_image, color_context, weight_function, num_inference_steps, guidance_scale,
+                         negative_prompt, seed, output_type, return_dict, callback, callback_steps)

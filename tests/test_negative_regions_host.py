@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import pww_cases as cases
+from host_standins import cpu_masks  # noqa: F401  (fixture)
 from oracle import pww_oracle as O
 
 SIDE = 64                                        # color map side: 64 / 16 / 4 / 1 tokens at ratios 8 / 16 / 32 / 64
@@ -33,37 +34,6 @@ def _color_map():
 def _tools():
     from sd_standin import HashTokenizer, TinyTextEncoder
     return TinyTextEncoder(32, seed=1235), HashTokenizer()
-
-
-@pytest.fixture
-def cpu_masks(monkeypatch):
-    """ops.mask_build / mask_build_f32 / gauss_blur as CPU stand-ins built from the oracle's restatements of the same steps."""
-    from pww_hip import ops
-
-    def build_f32(masks, cols, ratios=(8, 16, 32, 64)):
-        masks = masks.numpy()
-        H, W = masks.shape[1:]
-        outs = {}
-        for r in ratios:
-            hr, wr = O.always_round(H / r), O.always_round(W / r)
-            out = np.zeros((hr * wr, len(cols)), dtype=np.float32)
-            down = {}
-            for c, lst in enumerate(cols):
-                for reg in lst:
-                    if reg not in down:
-                        down[reg] = O.bilinear_resize(masks[reg], hr, wr, align_corners=True).reshape(-1)
-                    out[:, c] += down[reg]
-            outs[r] = torch.from_numpy(out)
-        return outs
-
-    def build(rgb, regions, cols, ratios=(8, 16, 32, 64)):
-        img = rgb.numpy()
-        masks = [(img == np.array(reg[:3], dtype=np.uint8)).all(-1).astype(np.float32) * np.float32(reg[3]) for reg in regions]
-        return build_f32(torch.from_numpy(np.stack(masks)), cols, ratios)
-
-    monkeypatch.setattr(ops, "mask_build", build)
-    monkeypatch.setattr(ops, "mask_build_f32", build_f32)
-    monkeypatch.setattr(ops, "gauss_blur", lambda mask, sigma, ksize=39: torch.from_numpy(O.gaussian_blur(mask.numpy(), sigma, ksize)))
 
 
 def _encode(neg, uncond_prompt=NEG_PROMPT, pos=None, prompt=POS_PROMPT, **kw):
