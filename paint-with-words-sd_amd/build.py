@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Three libraries come out of the same sources:
+Four libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`, and all that
                               __graft_entry__.build() compiles.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
@@ -12,6 +12,10 @@ Three libraries come out of the same sources:
   libpww_hip_long.so          the cross-attention launches of prompts longer than 77 tokens (128 < M <= 256 keys; include/pww_hip_long.h):
                               one translation unit over the same csrc/ headers, its own entry points (pww_long_*), loaded by the package on
                               the first long-prompt call. `build_long()`; __graft_entry__.build() compiles it beside the product library.
+  libpww_hip_scope.so         cross-attention whose bias coefficient is a per-head or per-row score statistic (M <= 128 keys;
+                              include/pww_hip_scope.h): one translation unit over the same csrc/ headers, its own entry points (pww_scope_*),
+                              loaded by the package on the first call of such a weight function. `build_scope()`; __graft_entry__.build()
+                              compiles it beside the other two.
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -25,6 +29,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "pww_hip", "libpww_hip.so")
 LIB_EXPERIMENTS = os.path.join(HERE, "pww_hip", "libpww_hip_experiments.so")
 LIB_LONG = os.path.join(HERE, "pww_hip", "libpww_hip_long.so")
+LIB_SCOPE = os.path.join(HERE, "pww_hip", "libpww_hip_scope.so")
 # (source, extra defines, object suffix): the instantiation units are compiled once per slice
 UNITS = [("pww_api.hip", [], ""), ("pww_attn.hip", [], ""), ("pww_cross.hip", [], ""), ("pww_cross_lean.hip", [], ""), ("pww_reduce.hip", [], ""),
          ("pww_mask.hip", [], ""), ("pww_qproj.hip", [], ""), ("pww_norm.hip", [], ""), ("pww_blocks.hip", [], ""), ("pww_conv.hip", [], ""), ("pww_probs.hip", [], ""),
@@ -34,6 +39,8 @@ UNITS = [("pww_api.hip", [], ""), ("pww_attn.hip", [], ""), ("pww_cross.hip", []
 EXPERIMENT_UNITS = [("pww_cross_out.hip", [], "")]      # sources only the experiments library has
 LONG_UNITS = [("pww_long.hip", ["-fvisibility=hidden"], "")]     # only the pww_long_* entry points are visible: a program may link both libraries
 LONG_HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_cross_tile.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_long.h")]
+SCOPE_UNITS = [("pww_scope.hip", ["-fvisibility=hidden"], "")]   # only the pww_scope_* entry points are visible
+SCOPE_HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_cross_tile.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_scope.h")]
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
 HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_attn_kernel.h", "pww_cross_tile.h", "pww_cross_kernel.h", os.path.join(REPO, "include", "pww_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -109,6 +116,14 @@ def build_long(force=False, verbose=False):
     return _build(LIB_LONG, LONG_UNITS, [], os.path.join(HERE, "build", "long"), verbose)
 
 
+def build_scope(force=False, verbose=False):
+    """libpww_hip_scope.so: cross-attention with per-head / per-row score statistics (include/pww_hip_scope.h)."""
+    deps = [os.path.join(CSRC, u[0]) for u in SCOPE_UNITS] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in SCOPE_HEADERS] + [__file__]
+    if not force and not _newer(LIB_SCOPE, deps):
+        return LIB_SCOPE
+    return _build(LIB_SCOPE, SCOPE_UNITS, [], os.path.join(HERE, "build", "scope"), verbose)
+
+
 def _build_check(exe, lib, libname, defines, force):
     src = os.path.join(REPO, "tests", "native", "attn_check.cpp")
     if not force and not _newer(exe, [src, lib, os.path.join(REPO, "include", "pww_hip.h")]):
@@ -134,6 +149,7 @@ if __name__ == "__main__":
     print(build_lib(force=force, verbose=True))
     print(build_native_check(force=force))
     print(build_long(force=force, verbose=True))
+    print(build_scope(force=force, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=force, verbose=True))
         print(build_native_check_experiments(force=force))

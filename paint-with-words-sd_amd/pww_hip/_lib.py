@@ -15,6 +15,10 @@ EXPERIMENTS_LIB_PATH = os.environ.get("PWW_HIP_EXPERIMENTS_LIB", os.path.join(_H
 # the launches of prompts longer than 77 tokens (128 < M <= 256 keys; include/pww_hip_long.h): loaded on the first long-prompt call (`load_long()`)
 LONG_LIB_PATH = os.environ.get("PWW_HIP_LONG_LIB", os.path.join(_HERE, "libpww_hip_long.so"))
 
+# cross-attention with a per-head / per-row score statistic (M <= 128 keys; include/pww_hip_scope.h): loaded on the first call of such a
+# weight function (`load_scope()`)
+SCOPE_LIB_PATH = os.environ.get("PWW_HIP_SCOPE_LIB", os.path.join(_HERE, "libpww_hip_scope.so"))
+
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 126        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
 DTYPE_F16, DTYPE_BF16 = 0, 1
@@ -40,6 +44,12 @@ LONG_EXPORTS = ("pww_long_version", "pww_long_last_error", "pww_long_qk_parts", 
                 "pww_long_cross_attn_probs", "pww_long_profile_arm", "pww_long_profile_elapsed_us")
 LONG_MIN_VERSION = 100
 LONG_MIN_KEYS, LONG_MAX_KEYS = 129, 256
+
+
+# every symbol include/pww_hip_scope.h declares for libpww_hip_scope.so
+SCOPE_EXPORTS = ("pww_scope_version", "pww_scope_last_error", "pww_scope_head_parts_count", "pww_scope_head_parts", "pww_scope_cross_attn_fwd")
+SCOPE_MIN_VERSION = 100
+SCOPE_HEAD, SCOPE_ROW = 1, 2
 
 
 class AttnDesc(ctypes.Structure):
@@ -268,6 +278,43 @@ def load_long():
     lib.pww_long_profile_elapsed_us.restype = ctypes.c_int
     _long = lib
     return _long
+
+
+_scope = None
+
+
+def load_scope():
+    """libpww_hip_scope.so (cross-attention with a per-head / per-row score statistic), loaded once, on the first call that asks for it.
+    Returns None when the file is missing: the caller keeps the materialised route, which computes the same thing. A file that is
+    there but stale or broken raises with the rebuild hint."""
+    global _scope
+    if _scope is not None:
+        return _scope
+    if not os.path.isfile(SCOPE_LIB_PATH):
+        return None
+    hint = "(rebuild: python paint-with-words-sd_amd/build.py)"
+    try:
+        lib = ctypes.CDLL(SCOPE_LIB_PATH)
+        lib.pww_scope_version.restype = ctypes.c_int
+        version = lib.pww_scope_version()
+    except (OSError, AttributeError) as e:
+        raise PwwHipError("libpww_hip_scope.so at %s cannot be loaded: %s %s" % (SCOPE_LIB_PATH, e, hint))
+    if version // 100 != 1 or version < SCOPE_MIN_VERSION:
+        raise PwwHipError("libpww_hip_scope ABI version %d is not 1.x >= %d %s" % (version, SCOPE_MIN_VERSION, hint))
+    missing = [n for n in SCOPE_EXPORTS if not hasattr(lib, n)]
+    if missing:
+        raise PwwHipError("libpww_hip_scope.so at %s lacks %s %s" % (SCOPE_LIB_PATH, missing, hint))
+    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
+    lib.pww_scope_last_error.restype = ctypes.c_char_p
+    lib.pww_last_error = lib.pww_scope_last_error        # (`check(rc, what, lib)` asks the library it is given)
+    lib.pww_scope_head_parts_count.argtypes = [ctypes.POINTER(AttnDesc)]
+    lib.pww_scope_head_parts_count.restype = ctypes.c_int32
+    lib.pww_scope_head_parts.argtypes = [vp, vp, vp, ctypes.POINTER(AttnDesc), i32, vp, ctypes.c_size_t, vp]
+    lib.pww_scope_head_parts.restype = ctypes.c_int
+    lib.pww_scope_cross_attn_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, vp, ctypes.POINTER(AttnDesc), vp, i32, vp, ctypes.POINTER(CrossOpts), vp]
+    lib.pww_scope_cross_attn_fwd.restype = ctypes.c_int
+    _scope = lib
+    return _scope
 
 
 class experiments:

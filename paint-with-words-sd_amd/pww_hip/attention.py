@@ -45,6 +45,11 @@ FUSED_CROSS = os.environ.get("PWW_FUSED_CROSS", "0") == "1"
 # heads run one after the other inside a workgroup where the two-launch route runs them on eight CUs. Round 6: NOT a product route any
 # more (no environment switch); the kernel lives in libpww_hip_experiments.so and the tests / tools set this flag themselves.
 FUSE_TO_OUT = False
+# Per-head / per-row score statistics (qk.amax(dim=(1, 2), keepdim=True), qk.std(dim=-1, keepdim=True), ...) on the launches of
+# libpww_hip_scope.so: default on; PWW_SCOPED_STATS=0 keeps such weight functions on the materialised route (Q K^T as a tensor, a dense
+# [B * heads, N, M] bias) -- tests and tools/time_scoped_stats.py compare the two routes in one process by setting this flag.
+SCOPED_STATS = os.environ.get("PWW_SCOPED_STATS", "1") != "0"
+SCOPE_IMAGE, SCOPE_HEAD, SCOPE_ROW = 0, ops.SCOPE_HEAD, ops.SCOPE_ROW      # what a LazyStat reduces over: all of an image's scores / one head's / one query row's
 QPROJ_STAT = os.environ.get("PWW_QPROJ_STAT", "1")       # "1" where it wins (default) | "0" never | "all" wherever the kernel supports the shape
 
 
@@ -74,16 +79,26 @@ class LazyStat:
     way (through ScaledW), the kernel forms the coefficient itself (pww_cross_attn_fwd_stat) and the three or four
     [B]-sized elementwise launches per cross-attention layer and step disappear. Any other use -- arithmetic with
     tensors, torch functions, .item(), comparison ... -- materialises the [B,1,1,1] / 0-dim fp32 tensor the old path
-    produced and carries on with it, unchanged."""
-    __slots__ = ("_proxy", "kind", "scale", "_t")
+    produced and carries on with it, unchanged.
 
-    def __init__(self, proxy, kind, scale=1.0):
+    scope: SCOPE_IMAGE (the global reductions above), SCOPE_HEAD (`qk.amax(dim=(1, 2), keepdim=True)` ...: stands for a [B*heads, 1, 1]
+    tensor) or SCOPE_ROW (`qk.std(dim=-1, keepdim=True)` ...: [B*heads, N, 1]). A scoped statistic remembers the call it came from and
+    materialises by making that very call on the materialised scores."""
+    __slots__ = ("_proxy", "kind", "scale", "_t", "scope", "_call")
+
+    def __init__(self, proxy, kind, scale=1.0, scope=SCOPE_IMAGE, call=None):
         self._proxy, self.kind, self.scale, self._t = proxy, kind, scale, None
+        self.scope, self._call = scope, call        # call = (method name, args, kwargs, on qk.abs()?) of a scoped reduction
 
     def stats(self):
         return self._proxy._st()
 
     def materialize(self):
+        if self._t is None and self.scope != SCOPE_IMAGE:
+            name, args, kw, absolute = self._call
+            full = self._proxy._materialize()
+            t = getattr(full.abs() if absolute else full, name)(*args, **kw)
+            self._t = t if self.scale == 1.0 else t * self.scale
         if self._t is None:
             st, n = self._proxy._st(), self._proxy._count()
             if self.kind == ops.STAT_MAX:
@@ -104,7 +119,7 @@ class LazyStat:
 
     def _times(self, other, divide=False):
         if isinstance(other, (int, float)) and not isinstance(other, bool):
-            return LazyStat(self._proxy, self.kind, self.scale / other if divide else self.scale * other)
+            return LazyStat(self._proxy, self.kind, self.scale / other if divide else self.scale * other, self.scope, self._call)
         return None
 
     def __mul__(self, other):
@@ -122,7 +137,7 @@ class LazyStat:
         return r if r is not None else self.materialize() / other
 
     def __neg__(self):
-        return LazyStat(self._proxy, self.kind, -self.scale)
+        return LazyStat(self._proxy, self.kind, -self.scale, self.scope, self._call)
 
     def __rtruediv__(self, other): return other / self.materialize()
     def __add__(self, other): return self.materialize() + other
@@ -147,6 +162,25 @@ class LazyStat:
     def __torch_function__(cls, func, types, args=(), kwargs=None):
         conv = lambda a: a.materialize() if isinstance(a, LazyStat) else a  # noqa: E731
         return func(*[conv(a) for a in args], **{k: conv(v) for k, v in (kwargs or {}).items()})
+
+
+def _reduction_scope(name, args, kw):
+    """SCOPE_HEAD / SCOPE_ROW if `qk.<name>(*args, **kw)` is one of the scoped reductions that stay symbolic -- dim = (1, 2) / (-2, -1)
+    (tuple or list, either order) or dim = 2 / -1, positional or by name, keepdim=True, for std the torch default (unbiased) -- else None."""
+    if any(k not in ("dim", "keepdim", "unbiased") for k in kw) or ("unbiased" in kw and (name != "std" or kw["unbiased"] is not True)):
+        return None
+    if len(args) > (1 if name == "std" else 2) or (args and "dim" in kw) or (len(args) == 2 and "keepdim" in kw):
+        return None
+    dim = args[0] if args else kw.get("dim")
+    keepdim = args[1] if len(args) == 2 else kw.get("keepdim", False)
+    if keepdim is not True:
+        return None
+    is_int = lambda x: isinstance(x, int) and not isinstance(x, bool)  # noqa: E731
+    if is_int(dim):
+        return SCOPE_ROW if dim in (2, -1) else None
+    if isinstance(dim, (tuple, list)) and len(dim) == 2 and all(is_int(x) and -3 <= x < 3 for x in dim):
+        return SCOPE_HEAD if sorted(x % 3 for x in dim) == [1, 2] else None
+    return None
 
 
 class QKProxy:
@@ -199,6 +233,20 @@ class QKProxy:
             return self._materialize().min(*args, **kw)
         return LazyStat(self, ops.STAT_MIN)
 
+    def _scoped(self, kind, name, args, kw, absolute=False):
+        """A per-head / per-row reduction: symbolic for the recognised spellings, else today's call on the materialised scores."""
+        scope = _reduction_scope(name, args, kw)
+        if scope is None:
+            full = self._materialize()
+            return getattr(full.abs() if absolute else full, name)(*args, **kw)
+        return LazyStat(self, kind, 1.0, scope, (name, args, dict(kw), absolute))
+
+    def amax(self, *args, **kw):
+        return self._scoped(ops.STAT_MAX, "amax", args, kw)
+
+    def amin(self, *args, **kw):
+        return self._scoped(ops.STAT_MIN, "amin", args, kw)
+
     def sum(self, *args, **kw):
         if args or kw:
             return self._materialize().sum(*args, **kw)
@@ -206,7 +254,7 @@ class QKProxy:
 
     def mean(self, *args, **kw):
         if args or kw:
-            return self._materialize().mean(*args, **kw)
+            return self._scoped(ops.STAT_MEAN, "mean", args, kw)
         return LazyStat(self, ops.STAT_MEAN)
 
     def var(self, *args, **kw):
@@ -218,7 +266,7 @@ class QKProxy:
 
     def std(self, *args, **kw):
         if args or kw:
-            return self._materialize().std(*args, **kw)
+            return self._scoped(ops.STAT_STD, "std", args, kw)
         return LazyStat(self, ops.STAT_STD)
 
     def abs(self):
@@ -316,6 +364,9 @@ class _AbsQK:
     def max(self):
         return LazyStat(self._p, ops.STAT_ABSMAX)
 
+    def amax(self, *args, **kw):
+        return self._p._scoped(ops.STAT_ABSMAX, "amax", args, kw, absolute=True)
+
     def __getattr__(self, name):
         return getattr(self._p._materialize().abs(), name)
 
@@ -349,6 +400,8 @@ class ScaledW:
         if not self._is_factor(factor):
             return None
         if torch.is_tensor(factor):
+            if self.stat is not None and self.stat.scope != SCOPE_IMAGE:
+                return None                                      # a tensor factor beside a per-head / per-row statistic: the real tensors
             factor = factor.to(torch.float32)
             if self.stat is not None:                            # a second tensor factor: fall back to tensors
                 return ScaledW(self.w, self.coeff * self.stat.materialize(), None)._scaled(factor, divide)
@@ -369,6 +422,8 @@ class ScaledW:
         return ScaledW(self.w, -self.coeff, self.stat)
 
     def materialize(self):
+        if self.stat is not None and self.stat.scope != SCOPE_IMAGE:
+            return (self.w * self.coeff) * self.stat.materialize()      # (the order of `c * w * g(sigma) * qk.amax(...)` on tensors)
         c = self.coeff if self.stat is None else self.coeff * self.stat.materialize()
         return self.w * c
 
@@ -417,7 +472,18 @@ def _symbolic_scalar(result):
     if isinstance(result, ScaledW) and not torch.is_tensor(result.coeff) and torch.is_tensor(result.w):
         if result.stat is None:
             return ops.STAT_NONE, float(result.coeff)
+        if result.stat.scope != SCOPE_IMAGE:
+            return None         # (a per-head / per-row statistic: _symbolic_scoped)
         return result.stat.kind, float(result.coeff) * float(result.stat.scale)
+    return None
+
+
+def _symbolic_scoped(result):
+    """(STAT_* kind, SCOPE_HEAD / SCOPE_ROW, python scalar) if a weight function's result is `c * w * stat(qk)` with a Python number c and a
+    per-head or per-row statistic, else None."""
+    if (isinstance(result, ScaledW) and not torch.is_tensor(result.coeff) and torch.is_tensor(result.w) and result.stat is not None
+            and result.stat.scope != SCOPE_IMAGE):
+        return result.stat.kind, result.stat.scope, float(result.coeff) * float(result.stat.scale)
     return None
 
 
@@ -432,7 +498,7 @@ class CoeffSlots:
     EVERY dict-context cross-attention call registers a site, also the ones whose weight function came back with no bias at all
     (a Python number, a 0-dim tensor, a bare statistic: kind NO_BIAS -- the captured graph then holds a bias-free kernel for that
     site). update() re-classifies every site each step and reports a change of class (no bias <-> symbolic, another statistic) as
-    "re-capture": a graph captured while `lambda w, s, qk: 0` (or a sigma-thresholded function's zero branch) was in force is
+    "re-capture" (a per-head / per-row statistic is its own class: kind = the pair (STAT_*, scope)): a graph captured while `lambda w, s, qk: 0` (or a sigma-thresholded function's zero branch) was in force is
     never replayed for a function that wants the bias."""
     MAX = 64
     NO_BIAS = -1
@@ -472,11 +538,15 @@ class CoeffSlots:
 
     @classmethod
     def classify(cls, result):
-        """(kind, scalar) of a weight function's result: (STAT_*, c) for c * w [* stat(qk)], (NO_BIAS, 0.0) when the result adds
+        """(kind, scalar) of a weight function's result: (STAT_*, c) for c * w [* stat(qk)], ((STAT_*, scope), c) for a per-head / per-row
+        statistic, (NO_BIAS, 0.0) when the result adds
         nothing softmax can see (Python number, 0-dim tensor, bare statistic), None for anything else (a tensor-valued bias)."""
         sym = _symbolic_scalar(result)
         if sym is not None:
             return sym
+        scoped = _symbolic_scoped(result)
+        if scoped is not None:
+            return (scoped[0], scoped[1]), scoped[2]        # the site's class is (statistic, scope)
         if isinstance(result, LazyStat) or isinstance(result, (int, float)) or (torch.is_tensor(result) and result.dim() == 0):
             return cls.NO_BIAS, 0.0
         return None
@@ -672,6 +742,22 @@ def _attention(attn, hidden_states, context, out_linear):
     rec = context.get(ATTN_RECORDER) if (context is not None and is_dict) else None
     if isinstance(bias, LazyStat):     # a bare statistic: a per-image constant on every logit of a row cancels in softmax
         bias = None
+    scoped = _symbolic_scoped(bias)
+    if scoped is not None:
+        # c0 * w * g(sigma) * reduce(qk over one head / one row): the launches of libpww_hip_scope.so form the coefficient themselves
+        # (stock to_q; the row gate is the per-image factor). Whatever they do not take carries on with the tensors, as before.
+        kind, scope, scalar = scoped
+        n_img, w_map = hidden_states.shape[1], bias.w
+        if _scoped_route(attn, key, w_map, kind, scope, rec, out_linear):
+            if query is None:
+                query = _half(lazy_q.get(), cdt)
+            if slots is not None and not slots.unsupported:
+                coeff_dev = slots.site((kind, scope), scalar, w_map, (hidden_states.shape[0] * attn.heads, n_img, key.shape[1]), cdt)
+            if scope == SCOPE_HEAD:
+                parts = ops.scope_head_parts(query, key, attn.heads, kind, gate=gate)
+            return ops.attention_scoped(query, key, value, attn.heads, attn.scale, w_map, kind, scope, scalar, gate=gate, parts=parts,
+                                        coeff_dev=coeff_dev), False
+        bias = bias.materialize()
     sym = _symbolic_scalar(bias)
     if sym is not None and (bias.stat is not None or slots is not None):
         # c0 * w * g(sigma) [* reduce(qk)]: map, statistic selector and Python scalar go to the kernel as they are. Over
@@ -785,6 +871,17 @@ def _attention(attn, hidden_states, context, out_linear):
     else:       # "plain": c[b] = gate[b]; "stat": the [B, 4] statistics came with the call
         _record_probs(rec, attn, context, query, key, bias, gate, stat, coeff_dev)
     return out, False
+
+
+def _scoped_route(attn, key, w_map, kind, scope, rec, out_linear):
+    """Does libpww_hip_scope.so take this call? (c * w * a per-head / per-row statistic: at most FUSED_MAX_KEYS keys, half-precision
+    q / k / v, no attention-map recorder, not the attention + to_out launch, the switch on, the library there, a shape it supports.)"""
+    if not SCOPED_STATS or rec is not None or out_linear is not None or key.dtype not in _HALF:
+        return False
+    M, D = key.shape[1], key.shape[2] // attn.heads
+    if M > ops.FUSED_MAX_KEYS or D % 8 or D > ops.MAX_HEAD_DIM or w_map.stride(-1) != 1 or (kind == ops.STAT_STD and M < 2):
+        return False
+    return ops.scoped_available()
 
 
 def _record_probs(rec, attn, context, query, key, bias, coeff, stat, coeff_dev):

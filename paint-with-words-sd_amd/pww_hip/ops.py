@@ -69,6 +69,7 @@ def _prep(t):
 
 STAT_NONE, STAT_MAX, STAT_MIN, STAT_MEAN, STAT_STD, STAT_ABSMAX, STAT_ALL = 0, 1, 2, 3, 4, 5, 6   # PWW_STAT_* of include/pww_hip.h
 FUSED_MAX_KEYS = 128   # pww_cross_attn_fwd_fused: one K/V stage
+MAX_HEAD_DIM = _lib.MAX_HEAD_DIM
 LONG_MAX_KEYS = _lib.LONG_MAX_KEYS   # libpww_hip_long.so: the same pair of launches for FUSED_MAX_KEYS < M <= 256 (prompts encoded in 2 / 3 chunks)
 COMPACT_MAX_R = 32     # pww_cross.hip: the compact form holds at most 32 non-zero columns
 
@@ -589,6 +590,83 @@ def long_qk_parts(q, k, heads, kind, gate=None, gated=0):
         _lib.check(lib.pww_long_qk_parts(_ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), int(gated or 0), _ptr(parts), parts.numel() * 8, _stream()),
                    "pww_long_qk_parts", lib)
     return parts
+
+
+SCOPE_HEAD, SCOPE_ROW = _lib.SCOPE_HEAD, _lib.SCOPE_ROW   # PWW_SCOPE_* of include/pww_hip_scope.h
+_SCOPED_KINDS = (STAT_MAX, STAT_MIN, STAT_MEAN, STAT_STD, STAT_ABSMAX)
+
+
+def scoped_available():
+    """True if libpww_hip_scope.so is there (a stale or broken file raises, with the rebuild hint)."""
+    return _lib.load_scope() is not None
+
+
+def _scope_lib():
+    lib = _lib.load_scope()
+    if lib is None:
+        raise PwwHipError("libpww_hip_scope.so not found at %s: per-head / per-row score statistics need it. Build it with "
+                          "`python paint-with-words-sd_amd/build.py` (or __graft_entry__.build())." % _lib.SCOPE_LIB_PATH)
+    return lib
+
+
+def scope_head_parts(q, k, heads, kind, gate=None):
+    """Partials of the score statistic of q k^T PER (image, head) over a finished q: float64 [B, heads, nparts, 4] = (max, min, sum, sum of
+    squares), the input of attention_scoped(..., scope=SCOPE_HEAD, parts=...). One small launch (pww_scope_head_parts, M <= 128).
+    gate: optional fp32 [B]; images with gate 0 get no partials (their rows are left as allocated)."""
+    _require_gpu(q, k, gate)
+    if q.dtype != k.dtype:
+        raise PwwHipError("scope_head_parts: dtypes differ: %s %s" % (q.dtype, k.dtype))
+    q, k = _prep(q), _prep(k)
+    d = _desc(q, k, None, None, heads, 1.0)
+    lib = _scope_lib()
+    nparts = int(lib.pww_scope_head_parts_count(ctypes.byref(d)))
+    if nparts <= 0:
+        raise PwwHipError("scope_head_parts: unsupported problem %s x %s, %d heads" % (tuple(q.shape), tuple(k.shape), heads))
+    B = q.shape[0]
+    parts = torch.empty((B, heads, nparts, 4), dtype=torch.float64, device=q.device)
+    gate = _per_image_f32(gate, B, "gate")
+    with torch.cuda.device(q.device):
+        _lib.check(lib.pww_scope_head_parts(_ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), _ptr(parts), parts.numel() * 8, _stream()),
+                   "pww_scope_head_parts", lib)
+    return parts
+
+
+def attention_scoped(q, k, v, heads, scale, bias, kind, scope, scalar, gate=None, parts=None, stats_out=None, coeff_dev=None):
+    """softmax((Q K^T + c * bias) * scale) V on [B, tokens, heads*D] tensors with the coefficient a statistic of the raw scores per head
+    (scope = SCOPE_HEAD: c[b][h] = scalar * stat(scores of image b, head h) * gate[b], folded from `parts` = scope_head_parts(q, k, ...))
+    or per query row (SCOPE_ROW: c[b][h][n] = scalar * stat(scores of that row) * gate[b], formed in registers: no partials).
+    bias: fp32 tensor broadcastable to [B, heads, N, M] with unit key stride; kind: STAT_MAX / MIN / MEAN / STD / ABSMAX; gate: optional
+    fp32 [B] per-image factor (0 = no bias for that image); coeff_dev: one-element fp32 device tensor that replaces `scalar` when the
+    kernel runs; stats_out (head scope): float64 [B, heads, 4] that receives the folded fields. M <= 128 (pww_scope_cross_attn_fwd)."""
+    _require_gpu(q, k, v, bias, gate, parts, stats_out)
+    if not (q.dtype == k.dtype == v.dtype):
+        raise PwwHipError("q/k/v dtypes differ: %s %s %s" % (q.dtype, k.dtype, v.dtype))
+    if bias is None:
+        raise PwwHipError("attention_scoped needs a bias map")
+    if scope not in (SCOPE_HEAD, SCOPE_ROW) or kind not in _SCOPED_KINDS:
+        raise PwwHipError("attention_scoped: scope %r / statistic %r outside SCOPE_HEAD, SCOPE_ROW / STAT_MAX ... STAT_ABSMAX" % (scope, kind))
+    q, k, v = _prep(q), _prep(k), _prep(v)
+    B, N, C = q.shape
+    out = torch.empty((B, N, C), dtype=q.dtype, device=q.device)
+    d = _desc(q, k, v, out, heads, scale)
+    if d.M > FUSED_MAX_KEYS:
+        raise PwwHipError("attention_scoped takes at most %d keys (got %d)" % (FUSED_MAX_KEYS, d.M))
+    bias = _bias_view(bias, d)
+    gate = _per_image_f32(gate, B, "gate", expand=True)
+    if scope == SCOPE_HEAD:
+        if parts is None:
+            raise PwwHipError("attention_scoped: head scope folds the partials of scope_head_parts")
+        _check_f64(parts, "parts", B, heads, "nparts", 4)
+        _check_f64(stats_out, "stats_out", B, heads, 4)
+    elif parts is not None or stats_out is not None:
+        raise PwwHipError("attention_scoped: row scope takes no partials and writes no stats_out")
+    op = _cross_opts(B, N, coeff_dev, 0, None)
+    lib = _scope_lib()
+    with torch.cuda.device(q.device):
+        _lib.check(lib.pww_scope_cross_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(bias), int(kind), int(scope), float(scalar), _ptr(gate),
+                                                ctypes.byref(d), _ptr(parts), int(parts.shape[2]) if parts is not None else 0, _ptr(stats_out),
+                                                _opt_ref(op), _stream()), "pww_scope_cross_attn_fwd", lib)
+    return out
 
 
 def fold_parts(parts):
