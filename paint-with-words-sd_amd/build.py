@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Four libraries come out of the same sources:
+Five libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`, and all that
                               __graft_entry__.build() compiles.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
@@ -16,6 +16,9 @@ Four libraries come out of the same sources:
                               include/pww_hip_scope.h): one translation unit over the same csrc/ headers, its own entry points (pww_scope_*),
                               loaded by the package on the first call of such a weight function. `build_scope()`; __graft_entry__.build()
                               compiles it beside the other two.
+  libpww_hip_linear.so        linear layers with a bias / residual / GEGLU epilogue (include/pww_hip_linear.h): one translation unit, its own
+                              entry points (pww_linear_*), loaded by the package on the first such call. `build_linear()`;
+                              __graft_entry__.build() compiles it beside the other three.
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -30,6 +33,7 @@ LIB = os.path.join(HERE, "pww_hip", "libpww_hip.so")
 LIB_EXPERIMENTS = os.path.join(HERE, "pww_hip", "libpww_hip_experiments.so")
 LIB_LONG = os.path.join(HERE, "pww_hip", "libpww_hip_long.so")
 LIB_SCOPE = os.path.join(HERE, "pww_hip", "libpww_hip_scope.so")
+LIB_LINEAR = os.path.join(HERE, "pww_hip", "libpww_hip_linear.so")
 # (source, extra defines, object suffix): the instantiation units are compiled once per slice
 UNITS = [("pww_api.hip", [], ""), ("pww_attn.hip", [], ""), ("pww_cross.hip", [], ""), ("pww_cross_lean.hip", [], ""), ("pww_reduce.hip", [], ""),
          ("pww_mask.hip", [], ""), ("pww_qproj.hip", [], ""), ("pww_norm.hip", [], ""), ("pww_blocks.hip", [], ""), ("pww_conv.hip", [], ""), ("pww_probs.hip", [], ""),
@@ -41,6 +45,8 @@ LONG_UNITS = [("pww_long.hip", ["-fvisibility=hidden"], "")]     # only the pww_
 LONG_HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_cross_tile.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_long.h")]
 SCOPE_UNITS = [("pww_scope.hip", ["-fvisibility=hidden"], "")]   # only the pww_scope_* entry points are visible
 SCOPE_HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_cross_tile.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_scope.h")]
+LINEAR_UNITS = [("pww_linear.hip", ["-fvisibility=hidden"], "")]  # only the pww_linear_* entry points are visible
+LINEAR_HEADERS = ["pww_common.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_linear.h")]
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
 HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_attn_kernel.h", "pww_cross_tile.h", "pww_cross_kernel.h", os.path.join(REPO, "include", "pww_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -124,6 +130,14 @@ def build_scope(force=False, verbose=False):
     return _build(LIB_SCOPE, SCOPE_UNITS, [], os.path.join(HERE, "build", "scope"), verbose)
 
 
+def build_linear(force=False, verbose=False):
+    """libpww_hip_linear.so: linear layers with a bias / residual / GEGLU epilogue (include/pww_hip_linear.h)."""
+    deps = [os.path.join(CSRC, u[0]) for u in LINEAR_UNITS] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in LINEAR_HEADERS] + [__file__]
+    if not force and not _newer(LIB_LINEAR, deps):
+        return LIB_LINEAR
+    return _build(LIB_LINEAR, LINEAR_UNITS, [], os.path.join(HERE, "build", "linear"), verbose)
+
+
 def _build_check(exe, lib, libname, defines, force):
     src = os.path.join(REPO, "tests", "native", "attn_check.cpp")
     if not force and not _newer(exe, [src, lib, os.path.join(REPO, "include", "pww_hip.h")]):
@@ -150,6 +164,7 @@ if __name__ == "__main__":
     print(build_native_check(force=force))
     print(build_long(force=force, verbose=True))
     print(build_scope(force=force, verbose=True))
+    print(build_linear(force=force, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=force, verbose=True))
         print(build_native_check_experiments(force=force))

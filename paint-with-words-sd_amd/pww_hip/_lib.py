@@ -19,11 +19,15 @@ LONG_LIB_PATH = os.environ.get("PWW_HIP_LONG_LIB", os.path.join(_HERE, "libpww_h
 # weight function (`load_scope()`)
 SCOPE_LIB_PATH = os.environ.get("PWW_HIP_SCOPE_LIB", os.path.join(_HERE, "libpww_hip_scope.so"))
 
+# linear layers with a bias / residual / GEGLU epilogue (include/pww_hip_linear.h): loaded on the first call of ops.linear (`load_linear()`)
+LINEAR_LIB_PATH = os.environ.get("PWW_HIP_LINEAR_LIB", os.path.join(_HERE, "libpww_hip_linear.so"))
+
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 126        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
 DTYPE_F16, DTYPE_BF16 = 0, 1
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 ACT_NONE, ACT_SILU = 0, 1
+LINEAR_NONE, LINEAR_BIAS, LINEAR_BIAS_RESIDUAL, LINEAR_BIAS_GEGLU = 0, 1, 2, 3
 MAX_HEAD_DIM = 160
 
 # every symbol include/pww_hip.h declares for libpww_hip.so (tests check the library exports all of them) ...
@@ -50,6 +54,11 @@ LONG_MIN_KEYS, LONG_MAX_KEYS = 129, 256
 SCOPE_EXPORTS = ("pww_scope_version", "pww_scope_last_error", "pww_scope_head_parts_count", "pww_scope_head_parts", "pww_scope_cross_attn_fwd")
 SCOPE_MIN_VERSION = 100
 SCOPE_HEAD, SCOPE_ROW = 1, 2
+
+
+# every symbol include/pww_hip_linear.h declares for libpww_hip_linear.so
+LINEAR_EXPORTS = ("pww_linear_version", "pww_linear_last_error", "pww_linear_workspace_bytes", "pww_linear_fwd")
+LINEAR_MIN_VERSION = 100
 
 
 class AttnDesc(ctypes.Structure):
@@ -92,6 +101,13 @@ class ConvDesc(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("Hin", ctypes.c_int32), ("Win", ctypes.c_int32),
                 ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32), ("stride", ctypes.c_int32), ("upsample", ctypes.c_int32), ("tile_n", ctypes.c_int32),
                 ("splitk", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class LinearDesc(ctypes.Structure):
+    """struct pww_linear_desc (linear layer with a bias / residual / GEGLU epilogue; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
+                ("epilogue", ctypes.c_int32), ("x_stride", ctypes.c_int64), ("y_stride", ctypes.c_int64), ("r_stride", ctypes.c_int64),
+                ("tile_n", ctypes.c_int32), ("splitk", ctypes.c_int32)]
 
 
 class ProbsDesc(ctypes.Structure):
@@ -315,6 +331,38 @@ def load_scope():
     lib.pww_scope_cross_attn_fwd.restype = ctypes.c_int
     _scope = lib
     return _scope
+
+
+_linear = None
+
+
+def load_linear():
+    """libpww_hip_linear.so (linear layers with a bias / residual / GEGLU epilogue), loaded once, on the first call that asks for it. A
+    missing kernel is an error: a file that is missing, stale or broken raises with the rebuild hint."""
+    global _linear
+    if _linear is not None:
+        return _linear
+    hint = "(rebuild: python paint-with-words-sd_amd/build.py)"
+    try:
+        lib = ctypes.CDLL(LINEAR_LIB_PATH)
+        lib.pww_linear_version.restype = ctypes.c_int
+        version = lib.pww_linear_version()
+    except (OSError, AttributeError) as e:
+        raise PwwHipError("libpww_hip_linear.so at %s cannot be loaded: %s %s" % (LINEAR_LIB_PATH, e, hint))
+    if version // 100 != 1 or version < LINEAR_MIN_VERSION:
+        raise PwwHipError("libpww_hip_linear ABI version %d is not 1.x >= %d %s" % (version, LINEAR_MIN_VERSION, hint))
+    missing = [n for n in LINEAR_EXPORTS if not hasattr(lib, n)]
+    if missing:
+        raise PwwHipError("libpww_hip_linear.so at %s lacks %s %s" % (LINEAR_LIB_PATH, missing, hint))
+    vp = ctypes.c_void_p
+    lib.pww_linear_last_error.restype = ctypes.c_char_p
+    lib.pww_last_error = lib.pww_linear_last_error        # (`check(rc, what, lib)` asks the library it is given)
+    lib.pww_linear_workspace_bytes.argtypes = [ctypes.POINTER(LinearDesc)]
+    lib.pww_linear_workspace_bytes.restype = ctypes.c_size_t
+    lib.pww_linear_fwd.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(LinearDesc), vp, ctypes.c_size_t, vp]
+    lib.pww_linear_fwd.restype = ctypes.c_int
+    _linear = lib
+    return _linear
 
 
 class experiments:

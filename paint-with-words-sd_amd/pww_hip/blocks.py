@@ -38,9 +38,9 @@ FUSED_NORM = os.environ.get("PWW_FUSED_NORM", "1") != "0"      # A/B switch (ben
 BATCHED_TEMB = os.environ.get("PWW_BATCHED_TEMB", "1") != "0"  # A/B switch: one time-embedding projection GEMM per forward for all blocks
 FOLD_CONV_BIAS = os.environ.get("PWW_FOLD_CONV_BIAS", "1") != "0"      # A/B: conv1 / conv2 biases of a ResnetBlock2D ride in the next fused op
 CONV1X1_AS_LINEAR = os.environ.get("PWW_CONV1X1_AS_LINEAR", "1") != "0"  # A/B: 1 x 1 convolutions on channels_last tensors as GEMMs
-# `ff(norm3(h)) + h` through the output GEMM's C operand (no add launch): built in round 5, measured NEUTRAL on the headline (4.04 / 4.06 vs 4.08 /
-# 4.06 images/s, profiles/r05_blocks_ab.md: hipBLASLt's beta = 1 kernels cost what the add launch saves) -> opt-in, off by default
-FUSE_FF_RESIDUAL = os.environ.get("PWW_FUSE_FF_RESIDUAL", "0") == "1"
+# A/B: the feed-forward GEMMs with GEGLU / the residual add in their epilogue (csrc/pww_linear.hip) where LINEAR_ROUTES says the HIP call wins.
+# "0": never; "force": every shape the kernel takes (tests, tools), whatever the table says
+LINEAR = os.environ.get("PWW_LINEAR", "1")
 CONV3X3 = os.environ.get("PWW_CONV3X3", "1") != "0"      # A/B: 3 x 3 convolutions on channels_last tensors on the HIP implicit-GEMM kernel
 
 
@@ -49,15 +49,16 @@ CONV3X3 = os.environ.get("PWW_CONV3X3", "1") != "0"      # A/B: 3 x 3 convolutio
 # passes and while a hipGraph is captured (a replay runs no Python). `stats()` returns a copy, `reset_stats()` zeroes; the first decline of
 # a HIP half-precision tensor per (op, reason) also warns once -- under torch.autocast, the reference's own run mode, the whole plug steps
 # aside (autocast runs the norms in fp32) and that is worth knowing when a benchmark claims the fused blocks.
-_STATS = {k: [0, 0] for k in ("group_norm", "resnet_block", "transformer_block", "geglu", "conv1x1", "conv3x3")}
-_UNRATED = ("conv1x1", "conv3x3")
+_STATS = {k: [0, 0] for k in ("group_norm", "resnet_block", "transformer_block", "geglu", "conv1x1", "conv3x3", "linear")}
+_UNRATED = ("conv1x1", "conv3x3", "linear")
 _warned = set()
 
 
 def stats():
     """{op: {"fused": n, "declined": n}} since the last reset_stats(), and the hit rate over the norm / elementwise ops (the 1 x 1
     and 3 x 3 convolutions are listed but not rated: an NCHW tensor keeps MIOpen's convolution by the caller's choice of memory format, and
-    the UNet's conv_in / conv_out have channel counts the kernel has no tile for)."""
+    the UNet's conv_in / conv_out have channel counts the kernel has no tile for; `linear` counts the GEMMs that were offered to the HIP
+    linear kernel: "declined" ones run as the stock GEMM by the measured route table)."""
     out = {k: {"fused": v[0], "declined": v[1]} for k, v in _STATS.items()}
     rated = [v for k, v in _STATS.items() if k not in _UNRATED]
     tot = sum(v[0] + v[1] for v in rated)
@@ -323,20 +324,20 @@ def _transformer_block_forward(self, *args, **kwargs):
     h = hidden_states
     n = ops.add_layer_norm(h, self.norm1.weight, self.norm1.bias, self.norm1.eps)
     h, n = ops.add_layer_norm(h, self.norm2.weight, self.norm2.bias, self.norm2.eps, a=self.attn1(n))
-    lin = _ff_output_linear(self.ff) if FUSE_FF_RESIDUAL else None
-    if lin is not None and lin.weight.dtype == h.dtype:
-        # `ff(norm3(h)) + h` without an add launch (round 5; 16 of the 32 residual adds of a forward): the sum that feeds norm3 leaves its
-        # launch already carrying the output GEMM's bias, and that GEMM adds it as its C operand (beta = 1)
-        h, n = ops.add_layer_norm(h, self.norm3.weight, self.norm3.bias, self.norm3.eps, a=self.attn2(n, context=context), post_bias=lin.bias)
-        g = self.ff.net[0](n)
-        return torch.addmm(h.reshape(-1, h.shape[-1]), g.reshape(-1, g.shape[-1]), lin.weight.t()).view(h.shape)
     h, n = ops.add_layer_norm(h, self.norm3.weight, self.norm3.bias, self.norm3.eps, a=self.attn2(n, context=context))
+    lin = _ff_output_linear(self.ff) if LINEAR != "0" else None
+    if lin is not None:
+        # `ff(norm3(h)) + h` with the add in the output GEMM's epilogue (no add launch), where the route table takes the shape
+        g = self.ff.net[0](n)
+        if _linear_route(g, lin.weight, lin.bias, "residual", residual=h):
+            return ops.linear(g, lin.weight, lin.bias, residual=h)
+        return lin(g) + h
     return self.ff(n) + h
 
 
 def _ff_output_linear(ff):
     """The output projection of a diffusers FeedForward `net = [GEGLU, Dropout, Linear]` when the block's tail can run as GEGLU -> one GEMM
-    with the residual as its C operand (a dropout that does nothing, a plain biased nn.Linear without hooks), else None."""
+    with the residual in its epilogue (a dropout that does nothing, a plain biased nn.Linear without hooks), else None."""
     net = getattr(ff, "net", None)
     # the stock class only: a subclass (or a patched class) that brings its own `forward` -- LoRA-scaled, chunked -- keeps it
     if net is None or len(net) != 3 or type(ff).__name__ != "FeedForward" or "forward" in ff.__dict__:
@@ -352,11 +353,42 @@ def _ff_output_linear(ff):
     return lin
 
 
+# (rows M, K, N, epilogue) of the SD1.5 UNet at 2 rows on which ops.linear measured faster than the stock sequence (hipBLASLt GEMM + pww_geglu, or
+# GEMM + add), replayed from a hipGraph on MI355X: tools/time_linear.py --sweep, profiles/linear_sweep.md. Everything else -- shapes outside
+# the table, shapes the stock route wins, the large M of the batch-8 configs -- keeps the stock GEMM.
+LINEAR_ROUTES = frozenset([
+    (8192, 320, 2560, "geglu"),        # 41.6 us against 51.5 (GEMM 35.0 + pww_geglu)
+    (2048, 640, 5120, "geglu"),        # 25.7 against 32.8
+    (512, 1280, 10240, "geglu"),       # 25.6 against 27.7
+    (128, 1280, 10240, "geglu"),       # 14.1 against 18.3
+    (512, 5120, 1280, "residual"),     # 21.5 against 24.4 (GEMM 21.8 + add); the output linears of the other levels lose: 26.1 / 19.1, 22.8 / 19.4, 14.0 / 13.4
+])
+
+
+def _linear_route(x, weight, bias, epilogue, residual=None):
+    """Whether this GEMM (x [..., K], weight [N, K], epilogue "geglu" / "residual") runs on the HIP linear kernel; counts the call either way
+    (not rated: see stats()). Operands the library would refuse (a misaligned bias, a residual whose rows have no common pitch of a multiple of
+    8 elements) decline to the stock GEMM like a shape outside the table. The table is keyed by shape alone, not by dtype: it was measured in
+    bf16, and an fp16 run of the same shapes takes the same routes without a timing of its own."""
+    ok = (LINEAR != "0" and FUSED_NORM and not torch.is_autocast_enabled() and torch.is_tensor(x) and bias is not None and bias.dtype == x.dtype
+          and not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)) and ops.linear_takes(x, weight, epilogue == "geglu", bias=bias, residual=residual)
+          and (LINEAR == "force" or (x.numel() // x.shape[-1], x.shape[-1], weight.shape[0], epilogue) in LINEAR_ROUTES))
+    _STATS["linear"][0 if ok else 1] += 1
+    return ok
+
+
+def _plain_linear(lin):
+    return type(lin) is nn.Linear and lin.bias is not None and not lin._forward_hooks and not lin._forward_pre_hooks and "forward" not in lin.__dict__
+
+
 def _geglu_forward(self, x, *args, **kwargs):
     """diffusers ``GEGLU.forward(hidden_states)``; later versions add ``scale`` (0.21 - 0.26): anything extra -> the module's own forward."""
     if args or kwargs:
         _count("geglu", False, x, "arguments beyond (hidden_states): %s" % (sorted(kwargs) or len(args)))
         return self._pww_orig_forward(x, *args, **kwargs)
+    if _plain_linear(self.proj) and _linear_route(x, self.proj.weight, self.proj.bias, "geglu"):
+        _count("geglu", True)
+        return ops.linear(x, self.proj.weight, self.proj.bias, geglu=True)          # projection and GEGLU: one kernel
     h = self.proj(x)
     if FUSED_NORM and h.is_cuda and h.dtype in (torch.float16, torch.bfloat16) and h.shape[-1] % 16 == 0 and not torch.is_autocast_enabled() \
             and not (torch.is_grad_enabled() and h.requires_grad):

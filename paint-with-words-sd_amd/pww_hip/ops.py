@@ -1042,3 +1042,83 @@ def conv3x3(x, weight, bias=None, residual=None, stride=1, upsample=False, tile_
     with torch.cuda.device(x.device):
         _lib.check(lib.pww_conv3x3_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(y), ctypes.byref(d), _ptr(ws), nbytes, _stream()), "pww_conv3x3_fwd")
     return y
+
+
+# ---- linear layers with the post-processing of the GEMM's output in its epilogue (csrc/pww_linear.hip, libpww_hip_linear.so) ------------
+def _linear_weight(weight):
+    """[N, K] view of an nn.Linear weight or of a 1 x 1 conv weight ([N, K, 1, 1]), in place; None when it is neither or not dense."""
+    if not torch.is_tensor(weight) or weight.dim() not in (2, 4) or (weight.dim() == 4 and tuple(weight.shape[2:]) != (1, 1)):
+        return None
+    w = weight.detach().reshape(weight.shape[0], weight.shape[1]) if weight.dim() == 4 else weight.detach()
+    return w if w.is_contiguous() and w.data_ptr() == weight.data_ptr() and w.data_ptr() % 16 == 0 else None
+
+
+def linear_takes(x, weight, geglu=False, bias=None, residual=None, out=None):
+    """True when pww_linear_fwd runs this call -- everything the library would answer PWW_ENOTSUP or PWW_EINVAL to is declined here: a
+    float16 / bfloat16 [..., K] x on a HIP device whose rows have one pitch (unit stride along K, a multiple of 8 elements, 16-byte aligned),
+    a dense [N, K] (or [N, K, 1, 1]) weight of its dtype, K and N multiples of 64 (geglu: N / 2 a multiple of 64); where given, a dense
+    8-byte aligned bias [N] of that dtype, and a residual / `out` of the output's shape and dtype whose rows have one such pitch too."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in _DT and x.dim() >= 2 and torch.is_tensor(weight) and weight.dtype == x.dtype):
+        return False
+    w = _linear_weight(weight)
+    if w is None or x.shape[-1] != w.shape[1] or x.numel() == 0 or _rows(x, "linear") is None:
+        return False
+    N, K = w.shape
+    rows, _, xs = _rows(x, "linear")
+    if not (K % 64 == 0 and N % (128 if geglu else 64) == 0 and rows * xs < 2 ** 31 and rows * N < 2 ** 31 and N * K < 2 ** 31):
+        return False
+    if bias is not None and not (torch.is_tensor(bias) and bias.is_cuda and bias.dtype == x.dtype and tuple(bias.shape) == (N,) and bias.is_contiguous()
+                                 and bias.data_ptr() % 8 == 0):
+        return False
+    shape = tuple(x.shape[:-1]) + (N // 2 if geglu else N,)
+    for t in (residual, out):
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == x.dtype and tuple(t.shape) == shape and _rows(t, "linear") is not None):
+            return False
+    return True
+
+
+def linear(x, weight, bias=None, residual=None, geglu=False, tile_n=0, splitk=0, out=None):
+    """F.linear(x, weight, bias) (+ residual), or with geglu=True GEGLU of it (`v * gelu(gate)`, [v | gate] = the two halves of the output
+    channels), on one HIP GEMM kernel (+ a fold launch when the K dimension is split). Rounding points: T(T(acc) + bias) (the accumulator is
+    rounded before the bias is added), then those of the unfused sequence on it: T(residual + that), T(v * T(gelu(gate))). weight: [N, K] or
+    a 1 x 1 conv weight [N, K, 1, 1], read in place. x, residual and `out` (default: a new dense tensor) are [..., C] tensors whose rows have
+    one pitch. tile_n / splitk: 0 = the library's choice."""
+    _require_gpu(x, weight, bias, residual, out)
+    if not linear_takes(x, weight, geglu):
+        raise PwwHipError("linear: needs a float16/bfloat16 [..., K] x with one row pitch and a dense [N, K] weight of its dtype, K and N multiples of 64%s"
+                          % (" (geglu: N / 2 a multiple of 64)" if geglu else ""))
+    w = _linear_weight(weight)
+    N, K = w.shape
+    M, _, xs = _rows(x, "linear")
+    nout = N // 2 if geglu else N
+    if (geglu or residual is not None) and bias is None:
+        raise PwwHipError("linear: the residual and GEGLU epilogues need the bias")
+    if geglu and residual is not None:
+        raise PwwHipError("linear: geglu and residual exclude each other")
+    if bias is not None:
+        if bias.dtype != x.dtype or tuple(bias.shape) != (N,):
+            raise PwwHipError("linear: bias must be a %s [%d]" % (x.dtype, N))
+        bias = bias.contiguous() if bias.data_ptr() % 8 == 0 else bias.clone(memory_format=torch.contiguous_format)
+    shape = tuple(x.shape[:-1]) + (nout,)
+    rs = 0
+    if residual is not None:
+        if tuple(residual.shape) != shape or residual.dtype != x.dtype:
+            raise PwwHipError("linear: residual must be a %s %s" % (x.dtype, shape))
+        r = _rows(residual, "linear")
+        if r is None:
+            residual = residual.contiguous()
+            r = _rows(residual, "linear")
+        rs = r[2]
+    if out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != x.dtype or _rows(out, "linear") is None:
+        raise PwwHipError("linear: out must be a %s %s whose rows have one pitch" % (x.dtype, shape))
+    ys = _rows(out, "linear")[2]
+    epi = _lib.LINEAR_BIAS_GEGLU if geglu else _lib.LINEAR_BIAS_RESIDUAL if residual is not None else _lib.LINEAR_BIAS if bias is not None else _lib.LINEAR_NONE
+    d = _lib.LinearDesc(ctypes.sizeof(_lib.LinearDesc), _DT[x.dtype], M, N, K, epi, xs, ys, rs, int(tile_n), int(splitk))
+    lib = _lib.load_linear()
+    nbytes = int(lib.pww_linear_workspace_bytes(ctypes.byref(d)))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    with torch.cuda.device(x.device):
+        _lib.check(lib.pww_linear_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(out), ctypes.byref(d), _ptr(ws), nbytes, _stream()), "pww_linear_fwd", lib)
+    return out

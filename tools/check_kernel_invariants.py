@@ -10,7 +10,10 @@ update, with correct results and slower kernels:
     for at the join: the prefetch becomes synchronous), the pass-1 loop waits with a COUNTED vmcnt (the ring of three blocks in flight
     survives), and the LDS-direct bias copies are issued back to back (inline asm: no wait between two copies).
 
+ 3. the linear-layer GEMM kernels (csrc/pww_linear.hip): the convolution tile's register budgets, no scratch.
+
     python tools/check_kernel_invariants.py            # prints one line per check, exit code 1 on a violation
+    python tools/check_kernel_invariants.py --only-linear   # the checks of csrc/pww_linear.hip alone (seconds instead of minutes)
 """
 import os
 import re
@@ -51,6 +54,24 @@ def kernel_isa(src, symbol_regex, extra=()):
     return out
 
 
+def check_linear(check):
+    """(K10) csrc/pww_linear.hip: the GEMM kernels keep the convolution tile's budgets -- 128-wide tile two workgroups per CU (<= 256 VGPRs,
+    2 waves per SIMD), 64-wide tile three (<= 168 VGPRs) -- and neither they nor the fold kernels use scratch."""
+    flags = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+    rows = resource_usage(os.path.join(CSRC, "pww_linear.hip"), flags)
+    seen = 0
+    for name, r in rows.items():
+        if "linear_kernel" in name:
+            wide = "Li128E" in name
+            seen += 1
+            check(int(r["ScratchSize [bytes/lane]"]) == 0 and int(r["VGPRs"]) <= (256 if wide else 168) and int(r["Occupancy [waves/SIMD]"]) >= (2 if wide else 3),
+                  "%s: %s VGPRs (<= %d), occupancy %s, %s B scratch (none)" % (name[:70], r["VGPRs"], 256 if wide else 168, r["Occupancy [waves/SIMD]"], r["ScratchSize [bytes/lane]"]))
+        elif "linear_fold_kernel" in name:
+            seen += 1
+            check(int(r["ScratchSize [bytes/lane]"]) == 0, "%s: %s VGPRs, %s B scratch (none)" % (name[:70], r["VGPRs"], r["ScratchSize [bytes/lane]"]))
+    check(seen == 6, "pww_linear.hip: %d code objects found (2 storage types x (2 tile widths + fold))" % seen)
+
+
 def main():
     bad = []
 
@@ -58,6 +79,11 @@ def main():
         print(("ok   " if ok else "FAIL ") + what)
         if not ok:
             bad.append(what)
+
+    if "--only-linear" in sys.argv:
+        check_linear(check)
+        print("%d violation(s)" % len(bad))
+        return 1 if bad else 0
 
     # ---- 1. register budgets -------------------------------------------------------------------------------------------------
     # (round 6: the kernel families are instantiated per storage type -- and the general cross kernel per workgroup width -- in
@@ -158,6 +184,7 @@ def main():
     acc = sum(1 for l in lines if l.startswith("v_accvgpr"))
     wf = sum(1 for i, l in enumerate(lines) if l.startswith("buffer_load") and any(x.startswith("s_cbranch_execnz") for x in lines[i + 1:i + 4]))      # (load; s_xor exec; s_cbranch_execnz = a waterfall loop)
     check(acc == 0 and wf == 0, "cross_out_kernel (bf16, d = 40): %d accumulator-file moves, %d buffer loads inside a waterfall loop (none)" % (acc, wf))
+    check_linear(check)
     print("%d violation(s)" % len(bad))
     return 1 if bad else 0
 
