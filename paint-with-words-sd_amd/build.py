@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Five libraries come out of the same sources:
+Six libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`, and all that
                               __graft_entry__.build() compiles.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
@@ -19,6 +19,9 @@ Five libraries come out of the same sources:
   libpww_hip_linear.so        linear layers with a bias / residual / GEGLU epilogue (include/pww_hip_linear.h): one translation unit, its own
                               entry points (pww_linear_*), loaded by the package on the first such call. `build_linear()`;
                               __graft_entry__.build() compiles it beside the other three.
+  libpww_hip_regions.so       region prompts (include/pww_hip_regions.h): the region masks at latent resolution and the per-pixel blend of
+                              the noise predictions, one translation unit, its own entry points (pww_regions_*), loaded by the package on
+                              the first call that carries region prompts. `build_regions()`; __graft_entry__.build() compiles it too.
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -34,6 +37,7 @@ LIB_EXPERIMENTS = os.path.join(HERE, "pww_hip", "libpww_hip_experiments.so")
 LIB_LONG = os.path.join(HERE, "pww_hip", "libpww_hip_long.so")
 LIB_SCOPE = os.path.join(HERE, "pww_hip", "libpww_hip_scope.so")
 LIB_LINEAR = os.path.join(HERE, "pww_hip", "libpww_hip_linear.so")
+LIB_REGIONS = os.path.join(HERE, "pww_hip", "libpww_hip_regions.so")
 # (source, extra defines, object suffix): the instantiation units are compiled once per slice
 UNITS = [("pww_api.hip", [], ""), ("pww_attn.hip", [], ""), ("pww_cross.hip", [], ""), ("pww_cross_lean.hip", [], ""), ("pww_reduce.hip", [], ""),
          ("pww_mask.hip", [], ""), ("pww_qproj.hip", [], ""), ("pww_norm.hip", [], ""), ("pww_blocks.hip", [], ""), ("pww_conv.hip", [], ""), ("pww_probs.hip", [], ""),
@@ -47,6 +51,8 @@ SCOPE_UNITS = [("pww_scope.hip", ["-fvisibility=hidden"], "")]   # only the pww_
 SCOPE_HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_cross_tile.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_scope.h")]
 LINEAR_UNITS = [("pww_linear.hip", ["-fvisibility=hidden"], "")]  # only the pww_linear_* entry points are visible
 LINEAR_HEADERS = ["pww_common.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_linear.h")]
+REGIONS_UNITS = [("pww_regions.hip", ["-fvisibility=hidden"], "")]  # only the pww_regions_* entry points are visible
+REGIONS_HEADERS = ["pww_common.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_regions.h")]
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
 HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_attn_kernel.h", "pww_cross_tile.h", "pww_cross_kernel.h", os.path.join(REPO, "include", "pww_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -57,8 +63,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
          "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
-# pww_mask.hip restates fp32 formulas that must match the CPU oracle bit for bit: no FMA contraction.
-PER_FILE_FLAGS = {"pww_mask.hip": ["-ffp-contract=off"]}
+# pww_mask.hip and pww_regions.hip restate fp32 formulas that must match a CPU restatement bit for bit: no FMA contraction.
+PER_FILE_FLAGS = {"pww_mask.hip": ["-ffp-contract=off"], "pww_regions.hip": ["-ffp-contract=off"]}
 
 
 def _newer(target, deps):
@@ -138,6 +144,14 @@ def build_linear(force=False, verbose=False):
     return _build(LIB_LINEAR, LINEAR_UNITS, [], os.path.join(HERE, "build", "linear"), verbose)
 
 
+def build_regions(force=False, verbose=False):
+    """libpww_hip_regions.so: region masks and the per-pixel blend of the noise predictions (include/pww_hip_regions.h)."""
+    deps = [os.path.join(CSRC, u[0]) for u in REGIONS_UNITS] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in REGIONS_HEADERS] + [__file__]
+    if not force and not _newer(LIB_REGIONS, deps):
+        return LIB_REGIONS
+    return _build(LIB_REGIONS, REGIONS_UNITS, [], os.path.join(HERE, "build", "regions"), verbose)
+
+
 def _build_check(exe, lib, libname, defines, force):
     src = os.path.join(REPO, "tests", "native", "attn_check.cpp")
     if not force and not _newer(exe, [src, lib, os.path.join(REPO, "include", "pww_hip.h")]):
@@ -165,6 +179,7 @@ if __name__ == "__main__":
     print(build_long(force=force, verbose=True))
     print(build_scope(force=force, verbose=True))
     print(build_linear(force=force, verbose=True))
+    print(build_regions(force=force, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=force, verbose=True))
         print(build_native_check_experiments(force=force))

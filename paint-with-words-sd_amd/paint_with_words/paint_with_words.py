@@ -22,6 +22,7 @@ from PIL import Image
 import pww_hip
 from pww_hip.attention import inj_forward  # noqa: F401  (same import path as the reference's symbol)
 from pww_hip.conditioning import check_prompt_chunks, prompt_chunk_count, check_negative_context
+from pww_hip.conditioning import check_region_prompts, region_entries, encode_region_prompts
 from pww_hip.conditioning import (always_round, _extract_seed_and_sigma_from_context, _encode_text_color_inputs,  # noqa: F401
                                   _get_binary_mask, gaussian_blur_mask)
 from pww_hip.sampler import PwWSampler, initial_latents
@@ -130,6 +131,12 @@ def _negative_contexts(negative_color_contexts, n, color_map_images):
     return negs, any(c is not None for c in negs)
 
 
+def _region_requests(region_prompts, n):
+    """-> one `region_prompts` dict per request, or None when no request carries one (None and {} are "off")."""
+    regs = list(region_prompts) if isinstance(region_prompts, (list, tuple)) else [region_prompts] * n
+    return regs if any(regs) else None
+
+
 def _batch_requests(n, color_contexts, negative_color_context, color_map_images, input_prompts, strip_color_contexts):
     """The per-request arguments a batch function shares with its twin -> (color contexts, negative contexts, color maps, prompts: n of
     each; `shared`: every request has the same four, so one conditioning serves all; the caller's dicts to strip after the call). Not
@@ -175,7 +182,8 @@ def _txt2img_or_img2img(sizes, init_images, strength):
 
 def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
               unconditional_input_prompt, start, strength=None, map_sizes=None, on_step=None, use_region_sigma=True, shared=False,
-              max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0):
+              max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0, region_prompts=None, region_base_weight=0.0,
+              region_feather=0.0):
     """The body behind every face of the package (reference :414-506, paint_with_words_inpaint.py:160-262): conditioning per request (once
     if `shared`: every request has the same map, context and prompt), the timesteps, the initial state, one denoise loop over all images.
     Returns the final latents [n, 4, h, w].
@@ -183,12 +191,14 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
     initial state: _seeded_noise, _noised_images or the inpaint module's _inpaint_start. strength: None runs every timestep (txt2img), a
     number the img2img tail of the schedule (:434-441). map_sizes: one (width, height) per request to resize its color map to (the inpaint
     function API, paint_with_words_inpaint.py:172). negative_color_contexts: None, or one dict (or None) per request like color_contexts --
-    regions of the unconditional prompt (see paint_with_words)."""
+    regions of the unconditional prompt (see paint_with_words). region_prompts: None, or one dict per request (_region_requests) -- a full
+    prompt per colour, blended per latent pixel where guidance is combined (see paint_with_words)."""
     unet, text_encoder, tokenizer, scheduler = tools[1:]
     n = len(seeds)
     sampler = _sampler_for(unet, scheduler)   # also installs the attention plug
     conds, unconds, seeds_info = [], [], []
-    min_chunks = _batch_prompt_chunks(tokenizer, (prompts[:1] if shared else prompts) + [unconditional_input_prompt], max_prompt_chunks)
+    region_texts = [e[1] for r in (region_prompts or []) for e in region_entries(r)]
+    min_chunks = _batch_prompt_chunks(tokenizer, (prompts[:1] if shared else prompts) + [unconditional_input_prompt] + region_texts, max_prompt_chunks)
     negs, any_neg = _negative_contexts(negative_color_contexts, n, color_map_images)
     for i in range(1 if shared else n):
         color_map = color_map_images[i]
@@ -199,6 +209,13 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
             dtype=_unet_dtype(unet), use_sigma=use_region_sigma, max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks,
             negative_color_context=negs[i], negative_maps=any_neg)
         conds.append(cond), unconds.append(uncond), seeds_info.append((extra_seeds, region_info))
+    regions = None
+    if region_prompts:
+        # one plan per request (one for all when the requests share everything): K more rows of the same UNet evaluation
+        one = shared and all(r is region_prompts[0] for r in region_prompts)
+        regions = [encode_region_prompts(text_encoder, tokenizer, device, seeds_info[0 if shared else i][1][1], region_prompts[i], guidance_scale,
+                                         unconds[0 if shared else i], dtype=_unet_dtype(unet), region_base_weight=region_base_weight,
+                                         region_feather=region_feather) for i in range(1 if one else n)]
     if shared:
         conds, unconds, seeds_info = conds[0], unconds[0], seeds_info * n
 
@@ -210,9 +227,10 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
         timesteps = timesteps[max(num_inference_steps - init_timestep + offset, 0):]
 
     latents, extra_channels = start(tools, device, seeds, timesteps, seeds_info)
+    more = {} if regions is None else {"regions": regions}        # (a call without region prompts is, argument for argument, the call of before)
     with pww_hip.miopen_find():
         return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra_channels,
-                              on_step=on_step, negative_strength=negative_strength)
+                              on_step=on_step, negative_strength=negative_strength, **more)
 
 
 def _finish(tools, latents, return_latents=False, decode=None):
@@ -248,6 +266,9 @@ def paint_with_words(
     return_latents: bool = False,
     negative_color_context: Optional[Dict[Tuple[int, int, int], str]] = None,
     negative_strength: float = 1.0,
+    region_prompts=None,
+    region_base_weight: float = 0.0,
+    region_feather: float = 0.0,
     max_prompt_chunks: int = 1,
 ):
     """reference :391-510. `return_latents=True` (extension) returns the final latent tensor instead
@@ -258,15 +279,25 @@ def paint_with_words(
     classifier-free guidance pushes away from the phrase inside its region. None / {} (the default) is the reference's unconditional pass.
     The dict is stripped of its seed / sigma tails like color_context. `max_prompt_chunks` (extension; 1, 2 or 3): a prompt longer than 75 tokens is
     encoded in up to that many 75-token chunks (154 / 231 keys) instead of cut at 77; with the default every request is tokenized as in
-    the reference, and a prompt that needs fewer chunks than the cap gets only the chunks it needs."""
+    the reference, and a prompt that needs fewer chunks than the cap gets only the chunks it needs.
+    `region_prompts` (extension; the reference's README lists "sentence wise text separation" as open): a full prompt per colour of the
+    color map, {(r, g, b): "prompt"} or {(r, g, b): ("prompt", weight in (0, 1], guidance_scale or None)}, 1 to 8 regions; the colours need
+    not appear in color_context. Every region prompt is one more row of each UNet evaluation (plain cross-attention, no token weights), and
+    the noise predictions are blended per latent pixel where guidance is combined: with M_k the share of the pixel's 8 x 8 block that has
+    colour k (feathered by a Gaussian of `region_feather` latent pixels, at most 8) and w_k = (1 - region_base_weight) weight_k M_k,
+    noise = e_u + (1 - sum w_k) g (e_prompt - e_u) + sum_k w_k s_k (e_k - e_u) -- `input_prompt` keeps the share `region_base_weight`
+    in [0, 1) inside the regions and everything outside them; s_k is region k's guidance scale (the call's by default). None / {} is the
+    call without the feature. Not combined with negative_color_context."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
+    check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context)
     color_map_image.size     # the reference dereferences it unconditionally (:414): None raises here too
     tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
     start, strength = _txt2img_or_img2img([color_map_image.size], None if init_image is None else [init_image], strength)
     latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps, guidance_scale,
                         weight_function, unconditional_input_prompt, start, strength, shared=True, max_prompt_chunks=max_prompt_chunks,
-                        negative_color_contexts=[negative_color_context], negative_strength=negative_strength)
+                        negative_color_contexts=[negative_color_context], negative_strength=negative_strength,
+                        region_prompts=_region_requests(region_prompts, 1), region_base_weight=region_base_weight, region_feather=region_feather)
     out = _finish(tools, latents, return_latents)
     return out if return_latents else out[0]
 
@@ -292,6 +323,9 @@ def paint_with_words_batch(
     return_latents: bool = False,
     negative_color_context: Union[None, Dict, Sequence[Optional[Dict]]] = None,
     negative_strength: float = 1.0,
+    region_prompts=None,
+    region_base_weight: float = 0.0,
+    region_feather: float = 0.0,
     max_prompt_chunks: int = 1,
 ):
     """len(seeds) requests through ONE denoise loop (the reference's multi-sample path is a
@@ -303,11 +337,13 @@ def paint_with_words_batch(
     color_context dicts are mutated like the single-image call mutates its dict (:296). Returns a list of PIL images
     (or the [n, 4, h, w] latents with return_latents=True). negative_color_context / negative_strength: see paint_with_words; one dict
     shared by every request or one (or None) per seed, like color_contexts. max_prompt_chunks: see paint_with_words; with per-image prompts
-    every image is padded (with empty chunks) to the largest chunk count of the batch."""
+    every image is padded (with empty chunks) to the largest chunk count of the batch. region_prompts / region_base_weight / region_feather:
+    see paint_with_words; one dict for all requests or one per seed, every request with the same number of regions."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     seeds = list(seeds)
     n = len(seeds)
+    check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context, n_requests=n)
     if n == 0:
         return []
     ctxs, negs, maps, prompts, shared, strip = _batch_requests(n, color_contexts, negative_color_context, color_map_images, input_prompts,
@@ -320,7 +356,8 @@ def paint_with_words_batch(
     start, strength = _txt2img_or_img2img([m.size for m in maps], inits, strength)
     latents = _generate(tools, device, ctxs, maps, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
                         unconditional_input_prompt, start, strength, shared=shared, max_prompt_chunks=max_prompt_chunks,
-                        negative_color_contexts=negs, negative_strength=negative_strength)
+                        negative_color_contexts=negs, negative_strength=negative_strength, region_prompts=_region_requests(region_prompts, n),
+                        region_base_weight=region_base_weight, region_feather=region_feather)
     for c in strip:
         _extract_seed_and_sigma_from_context(c)
     return _finish(tools, latents, return_latents)

@@ -25,7 +25,7 @@ from PIL import Image
 
 import pww_hip
 from .paint_with_words import (LMSDiscreteScheduler, _generate, _finish, _pil_from_latents, _txt2img_or_img2img, check_prompt_chunks,
-                               check_negative_context)
+                               check_negative_context, check_region_prompts, _region_requests)
 from .paint_with_words_inpaint import _inpaint_start
 
 _warned = set()
@@ -50,6 +50,11 @@ class PaintWithWord_StableDiffusionPipeline:
     # `negative_prompt`, read against the call's color map -- and `pipe.negative_strength`. Attributes for the same reason.
     negative_color_context = None
     negative_strength = 1.0
+    # extension: region prompts (see paint_with_words): `pipe.region_prompts = {(r, g, b): "full prompt"}` -- a prompt per colour of the call's
+    # color map, blended per latent pixel -- with `pipe.region_base_weight` and `pipe.region_feather`. Attributes for the same reason.
+    region_prompts = None
+    region_base_weight = 0.0
+    region_feather = 0.0
 
     def __init__(self, vae, text_encoder, tokenizer, unet, scheduler=None, safety_checker=None, feature_extractor=None,
                  requires_safety_checker: bool = False):
@@ -95,6 +100,7 @@ class PaintWithWord_StableDiffusionPipeline:
     def _check_extensions(self):
         check_prompt_chunks(self.max_prompt_chunks)
         check_negative_context(self.negative_color_context, self.negative_strength)
+        check_region_prompts(self.region_prompts, self.region_base_weight, self.region_feather, self.negative_color_context)
 
     def _check_inputs(self, prompt, height, width, negative_prompt, num_images_per_prompt, generator, latents, callback_steps):
         """The argument block both __call__s share (check_inputs of the diffusers base class, :431) -> (prompt, height, width,
@@ -125,7 +131,8 @@ class PaintWithWord_StableDiffusionPipeline:
         lat = _generate(tools, str(self.device), [color_context], [color_map_image], [prompt], [seed], num_inference_steps, guidance_scale,
                         weight_function, negative_prompt, start, strength, on_step=on_step, use_region_sigma=False, shared=True,
                         max_prompt_chunks=self.max_prompt_chunks, negative_color_contexts=[self.negative_color_context],
-                        negative_strength=self.negative_strength)
+                        negative_strength=self.negative_strength, region_prompts=_region_requests(self.region_prompts, 1),
+                        region_base_weight=self.region_base_weight, region_feather=self.region_feather)
         images = _finish(tools, lat, decode=lambda vae, latents: _decode(vae, latents, output_type))
         return SimpleNamespace(images=images, nsfw_content_detected=False) if return_dict else (images, False)
 

@@ -22,6 +22,10 @@ SCOPE_LIB_PATH = os.environ.get("PWW_HIP_SCOPE_LIB", os.path.join(_HERE, "libpww
 # linear layers with a bias / residual / GEGLU epilogue (include/pww_hip_linear.h): loaded on the first call of ops.linear (`load_linear()`)
 LINEAR_LIB_PATH = os.environ.get("PWW_HIP_LINEAR_LIB", os.path.join(_HERE, "libpww_hip_linear.so"))
 
+# region prompts: the region masks at latent resolution and the per-pixel blend of the noise predictions (include/pww_hip_regions.h): loaded on
+# the first call that carries region prompts (`load_regions()`)
+REGIONS_LIB_PATH = os.environ.get("PWW_HIP_REGIONS_LIB", os.path.join(_HERE, "libpww_hip_regions.so"))
+
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 126        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
 DTYPE_F16, DTYPE_BF16 = 0, 1
@@ -59,6 +63,12 @@ SCOPE_HEAD, SCOPE_ROW = 1, 2
 # every symbol include/pww_hip_linear.h declares for libpww_hip_linear.so
 LINEAR_EXPORTS = ("pww_linear_version", "pww_linear_last_error", "pww_linear_workspace_bytes", "pww_linear_fwd")
 LINEAR_MIN_VERSION = 100
+
+
+# every symbol include/pww_hip_regions.h declares for libpww_hip_regions.so
+REGIONS_EXPORTS = ("pww_regions_version", "pww_regions_last_error", "pww_regions_masks", "pww_regions_combine")
+REGIONS_MIN_VERSION = 100
+REGIONS_MAX, REGIONS_MAX_PLANE, REGIONS_MAX_FEATHER = 8, 9216, 8.0      # PWW_REGIONS_MAX* of the header
 
 
 class AttnDesc(ctypes.Structure):
@@ -363,6 +373,38 @@ def load_linear():
     lib.pww_linear_fwd.restype = ctypes.c_int
     _linear = lib
     return _linear
+
+
+_regions = None
+
+
+def load_regions():
+    """libpww_hip_regions.so (region masks and the per-pixel blend of the noise predictions), loaded once, on the first call that carries
+    region prompts. A missing kernel is an error: a file that is missing, stale or broken raises with the rebuild hint."""
+    global _regions
+    if _regions is not None:
+        return _regions
+    hint = "(rebuild: python paint-with-words-sd_amd/build.py)"
+    try:
+        lib = ctypes.CDLL(REGIONS_LIB_PATH)
+        lib.pww_regions_version.restype = ctypes.c_int
+        version = lib.pww_regions_version()
+    except (OSError, AttributeError) as e:
+        raise PwwHipError("libpww_hip_regions.so at %s cannot be loaded: %s %s" % (REGIONS_LIB_PATH, e, hint))
+    if version // 100 != 1 or version < REGIONS_MIN_VERSION:
+        raise PwwHipError("libpww_hip_regions ABI version %d is not 1.x >= %d %s" % (version, REGIONS_MIN_VERSION, hint))
+    missing = [n for n in REGIONS_EXPORTS if not hasattr(lib, n)]
+    if missing:
+        raise PwwHipError("libpww_hip_regions.so at %s lacks %s %s" % (REGIONS_LIB_PATH, missing, hint))
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    lib.pww_regions_last_error.restype = ctypes.c_char_p
+    lib.pww_last_error = lib.pww_regions_last_error        # (`check(rc, what, lib)` asks the library it is given)
+    lib.pww_regions_masks.argtypes = [vp, i32, i32, vp, i32, f32, vp, vp]
+    lib.pww_regions_masks.restype = ctypes.c_int
+    lib.pww_regions_combine.argtypes = [vp, vp, vp, vp, f32, vp, i32, i32, i32, i64, i32, vp]
+    lib.pww_regions_combine.restype = ctypes.c_int
+    _regions = lib
+    return _regions
 
 
 class experiments:

@@ -110,6 +110,123 @@ def check_negative_context(negative_color_context, negative_strength=1.0):
                              "\"phrase,strength,-1,sigma\"" % ", ".join(str(v) for v in seeds.values()))
 
 
+MAX_REGION_PROMPTS = 8       # region prompts per request (PWW_REGIONS_MAX of include/pww_hip_regions.h)
+MAX_REGION_FEATHER = 8.0     # sigma of the feather of the region masks, in latent pixels (PWW_REGIONS_MAX_FEATHER)
+
+
+def _rgb_of(color):
+    """(r, g, b) of a key of color_context / region_prompts: a tuple of three 8-bit ints, or "#rrggbb"."""
+    if isinstance(color, str):
+        if len(color) != 7 or color[0] != "#":
+            raise ValueError("region_prompts: colour %r is not (r, g, b) or \"#rrggbb\"" % (color,))
+        try:
+            return tuple(int(color[i:i + 2], 16) for i in (1, 3, 5))
+        except ValueError:
+            raise ValueError("region_prompts: colour %r is not (r, g, b) or \"#rrggbb\"" % (color,))
+    if (not isinstance(color, (tuple, list)) or len(color) != 3
+            or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) <= 255 for c in color)):
+        raise ValueError("region_prompts: colour %r is not (r, g, b) with 8-bit values or \"#rrggbb\"" % (color,))
+    return tuple(int(c) for c in color)
+
+
+def _number(v, name):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+        raise ValueError("%s must be a finite number (got %r)" % (name, v))
+    return float(v)
+
+
+def region_entries(region_prompts):
+    """One request's `region_prompts` dict -> [((r, g, b), prompt, weight, guidance_scale or None)], checked: 1 .. MAX_REGION_PROMPTS
+    entries {colour: "full prompt"} or {colour: ("full prompt", weight in (0, 1], guidance_scale or None)}, no colour twice."""
+    if not isinstance(region_prompts, dict):
+        raise ValueError("region_prompts must be a dict {(r, g, b): \"prompt\"} or {(r, g, b): (\"prompt\", weight, guidance_scale)} (got %r)"
+                         % type(region_prompts).__name__)
+    if not 1 <= len(region_prompts) <= MAX_REGION_PROMPTS:
+        raise ValueError("region_prompts takes 1 to %d regions (got %d)" % (MAX_REGION_PROMPTS, len(region_prompts)))
+    out = []
+    for color, value in region_prompts.items():
+        rgb = _rgb_of(color)
+        if rgb in [e[0] for e in out]:
+            raise ValueError("region_prompts names colour %s twice" % (rgb,))
+        fields = (value,) if isinstance(value, str) else value
+        if not isinstance(fields, (tuple, list)) or not 1 <= len(fields) <= 3 or not isinstance(fields[0], str):
+            raise ValueError("region_prompts[%s] must be a prompt or (prompt, weight, guidance_scale) (got %r)" % (rgb, value))
+        weight = _number(fields[1], "region_prompts[%s]: weight" % (rgb,)) if len(fields) > 1 else 1.0
+        if not 0.0 < weight <= 1.0:
+            raise ValueError("region_prompts[%s]: weight must be in (0, 1] (got %r)" % (rgb, weight))
+        scale = fields[2] if len(fields) > 2 else None
+        if scale is not None:
+            scale = _number(scale, "region_prompts[%s]: guidance_scale" % (rgb,))
+        out.append((rgb, fields[0], weight, scale))
+    return out
+
+
+def check_region_prompts(region_prompts, region_base_weight=0.0, region_feather=0.0, negative_color_context=None, n_requests=None):
+    """The `region_prompts` / `region_base_weight` / `region_feather` keywords of the entry points, checked before any model is touched.
+    region_prompts: None or {} (off), one dict (region_entries), or -- the batch forms, `n_requests` given -- a sequence with one dict (or
+    None) per request; every request of one call carries the same number of regions. Together with a non-empty negative_color_context it is
+    refused. Returns the number of regions per request (0: off)."""
+    beta = _number(region_base_weight, "region_base_weight")
+    if not 0.0 <= beta < 1.0:
+        raise ValueError("region_base_weight must be in [0, 1) (got %r)" % (region_base_weight,))
+    feather = _number(region_feather, "region_feather")
+    if not 0.0 <= feather <= MAX_REGION_FEATHER:
+        raise ValueError("region_feather must be in [0, %g] latent pixels (got %r)" % (MAX_REGION_FEATHER, region_feather))
+    if region_prompts is None:
+        return 0
+    if isinstance(region_prompts, (list, tuple)):
+        if n_requests is None:
+            raise ValueError("region_prompts must be a dict (a sequence of dicts is the batch form)")
+        if len(region_prompts) != n_requests:
+            raise ValueError("region_prompts has %d entries for %d requests" % (len(region_prompts), n_requests))
+        per = list(region_prompts)
+    else:
+        per = [region_prompts]
+    counts = [0 if r is None or (isinstance(r, dict) and not r) else len(region_entries(r)) for r in per]
+    if len(set(counts)) > 1:
+        raise ValueError("region_prompts: every request of one call must carry the same number of regions (got %s)" % counts)
+    if counts and counts[0]:
+        negs = negative_color_context if isinstance(negative_color_context, (list, tuple)) else [negative_color_context]
+        if any(negs):
+            raise ValueError("region_prompts together with a negative_color_context is not supported")
+    return counts[0] if counts else 0
+
+
+def encode_region_prompts(text_encoder, tokenizer, device, color_map_rgb, region_prompts, guidance_scale, like, dtype=None,
+                          region_base_weight=0.0, region_feather=0.0):
+    """One request's region prompts -> its plan for the sampler:
+      "contexts"  K dicts built like the reference's unconditional dict (:355-357): the region prompt's embedding and the integer 0 in every
+                  weight slot of `like` (the request's unconditional dict) -- plain cross-attention. Encoded to the chunk count of `like`.
+      "masks"     fp32 [K, h, w] (ops.region_masks): the share of each latent pixel's 8 x 8 pixel block that has the region's colour,
+                  feathered by `region_feather`
+      "weights"   fp32 [K]: weight_k (1 - region_base_weight), formed in fp32
+      "scales"    fp32 [K]: the region's guidance scale, the call's where it is None."""
+    entries = region_entries(region_prompts)
+    if color_map_rgb is None:
+        raise ValueError("region_prompts need a color map")
+    L = tokenizer.model_max_length
+    k = like["CONTEXT_TENSOR"].shape[1] // L
+    contexts = []
+    for _, prompt, _, _ in entries:
+        if k <= 1:
+            ids = tokenizer([prompt], padding="max_length", max_length=L, truncation=True, return_tensors="pt").input_ids
+            emb = text_encoder(ids.to(device))[0]
+        else:
+            _, rows = chunk_prompt(tokenizer, prompt, k, k)
+            emb = torch.cat([text_encoder(torch.tensor([row], dtype=torch.long).to(device))[0] for row in rows], dim=1)
+        if dtype is not None:
+            emb = emb.to(dtype)
+        ctx = {"CONTEXT_TENSOR": emb}
+        ctx.update({key: 0 for key in dict.keys(like) if key.startswith("CROSS_ATTENTION_WEIGHT_")})
+        contexts.append(ctx)
+    rgb = torch.as_tensor(np.ascontiguousarray(color_map_rgb), dtype=torch.uint8).to(device)
+    masks = ops.region_masks(rgb, [e[0] for e in entries], float(region_feather))
+    keep = np.float32(1.0) - np.float32(region_base_weight)
+    weights = torch.from_numpy(np.array([keep * np.float32(e[2]) for e in entries], dtype=np.float32))
+    scales = torch.tensor([float(guidance_scale) if e[3] is None else e[3] for e in entries], dtype=torch.float32)
+    return {"contexts": contexts, "masks": masks, "weights": weights.to(device), "scales": scales.to(device)}
+
+
 def _parse_regions(color_context, tokenizer):
     """Host half of _image_context_seperator (:218-230): [(token_ids, (r, g, b), strength)]."""
     table = []

@@ -849,6 +849,49 @@ def cfg_combine(cond, uncond, guidance_scale):
     return out
 
 
+# ---- region prompts (libpww_hip_regions.so, include/pww_hip_regions.h) -------------------------------------------------------------------
+def region_masks(rgb, colors, feather=0.0):
+    """uint8 colour map [H, W, 3] (device) + K (r, g, b) colours -> fp32 [K, H // 8, W // 8]: per latent pixel the share of its 8 x 8 pixel
+    block that has colour k exactly, feathered by a Gaussian of sigma `feather` latent pixels if that is > 0. One launch."""
+    _require_gpu(rgb)
+    if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise PwwHipError("region_masks needs a uint8 colour map [H, W, 3]")
+    rgb = rgb.contiguous()
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    K = len(colors)
+    flat = [int(v) for c in colors for v in c]
+    if len(flat) != 3 * K or any(not 0 <= v <= 255 for v in flat):
+        raise PwwHipError("region_masks needs (r, g, b) colours of 8-bit values")
+    host = (ctypes.c_uint8 * max(len(flat), 1))(*flat)
+    out = torch.empty((K, H // 8, W // 8), dtype=torch.float32, device=rgb.device)
+    lib = _lib.load_regions()
+    with torch.cuda.device(rgb.device):
+        _lib.check(lib.pww_regions_masks(_ptr(rgb), H, W, host, K, float(feather), _ptr(out), _stream()), "pww_regions_masks", lib)
+    return out
+
+
+def region_combine(eps, masks, weights, scales, guidance_scale):
+    """The blend of one step's noise predictions (returns fp32 [n, C, h, w]): eps [(K + 2) n, C, h, w] float16 / bfloat16 with rows
+    [base x n, region 1 x n, ..., region K x n, unconditional x n], masks fp32 [n, K, h, w], weights / scales fp32 [n, K]:
+    e_u + w_0 g (e_0 - e_u) + sum_k w_k s_k (e_k - e_u) with w_k = weights[k] * masks[k] and w_0 = 1 - sum_k w_k, in fp32, in that order."""
+    _require_gpu(eps, masks, weights, scales)
+    if eps.dtype not in _DT or eps.dim() != 4 or masks.dim() != 4:
+        raise PwwHipError("region_combine needs a float16 / bfloat16 [(K + 2) n, C, h, w] tensor and fp32 masks [n, K, h, w]")
+    n, K = int(masks.shape[0]), int(masks.shape[1])
+    if (eps.shape[0] != (K + 2) * n or tuple(eps.shape[-2:]) != tuple(masks.shape[-2:]) or tuple(weights.shape) != (n, K) or tuple(scales.shape) != (n, K)
+            or any(t.dtype != torch.float32 for t in (masks, weights, scales))):
+        raise PwwHipError("region_combine: eps %s does not go with masks %s, weights %s and scales %s (fp32)"
+                          % (tuple(eps.shape), tuple(masks.shape), tuple(weights.shape), tuple(scales.shape)))
+    eps, masks, weights, scales = eps.contiguous(), masks.contiguous(), weights.contiguous(), scales.contiguous()
+    C, h, w = (int(v) for v in eps.shape[1:])
+    out = torch.empty((n, C, h, w), dtype=torch.float32, device=eps.device)
+    lib = _lib.load_regions()
+    with torch.cuda.device(eps.device):
+        _lib.check(lib.pww_regions_combine(_ptr(eps), _ptr(masks), _ptr(weights), _ptr(scales), float(guidance_scale), _ptr(out), n, K, C, h * w,
+                                           _DT[eps.dtype], _stream()), "pww_regions_combine", lib)
+    return out
+
+
 # ---- GroupNorm (+ per-(image, channel) addend, + SiLU) of the blocks that call the attention path ------------------------------------
 def group_norm(x, num_groups, weight=None, bias=None, eps=1e-5, add=None, act=None, workspace=None, out=None, pre_bias=None):
     """act(GroupNorm(x + add[:, :, None, None])) for a [B, C, H, W] float16 / bfloat16 tensor in NCHW-contiguous or channels_last memory

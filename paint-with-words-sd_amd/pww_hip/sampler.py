@@ -14,6 +14,9 @@ Three execution modes over the SAME arithmetic:
             weight_function produces -- live in device words (attention.CoeffSlots) that the host
             rewrites before each replay. A weight function that is not of the form
             c * w * reduce(qk) bakes sigma into torch ops; the sampler then keeps one graph per step.
+Region prompts (a full prompt per colour, `regions=`) add K rows per image in each of the three: K more batch-1 calls in "eager", rows
+[base x n, region 1 x n, ..., region K x n, uncond x n] in "folded" / "graph" (_fold_regions), and the per-pixel blend of
+ops.region_combine where classifier-free guidance is combined otherwise.
 """
 import torch
 
@@ -95,6 +98,71 @@ def _fold_negative(conds, unconds, folded, n_images, negative_strength, device):
     return folded
 
 
+def _context_rows(dicts, n_images):
+    """The CONTEXT_TENSOR rows of one row class of a folded call: [n, T, ctx]."""
+    if all(d is dicts[0] for d in dicts):
+        t = dicts[0]["CONTEXT_TENSOR"]
+        return t.expand(n_images, -1, -1) if t.shape[0] == 1 else t
+    return torch.cat([d["CONTEXT_TENSOR"] for d in dicts], dim=0)
+
+
+def _fold_regions(cond, regions, uncond, n_images, device):
+    """The single dict of a folded call with region prompts: rows [base x n, region 1 x n, ..., region K x n, uncond x n]. `regions`: one
+    plan (conditioning.encode_region_prompts) or one per image, all with the same K. Only the base rows are biased: the gate is ones for the
+    first n rows and zeros after, the work-distribution hint is n, and whatever _fold_context stacked per image (weight maps, the
+    full-resolution fallback map, the compact forms) is padded with zeros (column index -1) for every row past n."""
+    conds, plans = _as_list(cond, n_images), _as_list(regions, n_images)
+    K = len(plans[0]["contexts"])
+    if K < 1 or any(len(p["contexts"]) != K for p in plans):
+        raise ValueError("region prompts: every image of one call must carry the same number of regions (got %s)" % [len(p["contexts"]) for p in plans])
+    folded = _fold_context(cond, uncond, n_images, device)
+    if folded.get(GATED_ROWS) != n_images:
+        raise ValueError("region prompts do not combine with negative regions")
+    n, extra = n_images, (K + 1) * n_images
+    ct = folded["CONTEXT_TENSOR"]
+    region_rows = [_context_rows([p["contexts"][k] for p in plans], n) for k in range(K)]
+    shapes = {tuple(r.shape[1:]) for r in region_rows} | {tuple(ct.shape[1:])}
+    if len(shapes) != 1:
+        raise ValueError("region prompts: every prompt of one call must be encoded to the same number of chunks (got %s)" % sorted(shapes))
+    folded["CONTEXT_TENSOR"] = torch.cat([ct[:n]] + region_rows + [ct[n:]], dim=0).contiguous()
+    folded[ROW_GATE] = torch.cat([torch.ones(n), torch.zeros(extra)]).to(device=device, dtype=torch.float32)
+    if all(c is conds[0] for c in conds):
+        return folded                       # shared maps stay [N, T]: the gate keeps them off every row past n
+
+    def pad(t, fill=0):
+        return torch.cat([t[:n], t.new_full((extra,) + tuple(t.shape[1:]), fill)], dim=0).contiguous()
+    if folded.pending(ORIG):
+        stacked = folded._thunks[ORIG]
+        folded.set_lazy(ORIG, lambda: pad(stacked()))
+    for key in list(dict.keys(folded)):
+        v = dict.get(folded, key)
+        if not torch.is_tensor(v) or v.shape[0] != 2 * n:
+            continue
+        if key.startswith("CROSS_ATTENTION_WEIGHT_") and v.dim() == 4:
+            folded[key] = pad(v)
+        elif key.startswith(COMPACT_W) and v.dim() == 3:
+            folded[key] = pad(v)
+        elif key == COMPACT_IDX:
+            folded[key] = pad(v, -1)
+    return folded
+
+
+def region_blend_fp32(eps, masks, weights, scales, guidance_scale):
+    """ops.region_combine's formula on fp32 tensors, operation by operation (include/pww_hip_regions.h): what a UNet that runs in fp32 is
+    combined with, as `uncond + g * (cond - uncond)` is without regions."""
+    n, K = masks.shape[:2]
+    e = eps.float().reshape((K + 2, n) + tuple(eps.shape[1:]))
+    u = e[K + 1]
+    wk = [weights[:, k, None, None] * masks[:, k] for k in range(K)]            # [n, h, w] each
+    total = wk[0]
+    for k in range(1, K):
+        total = total + wk[k]
+    acc = u + ((1.0 - total) * float(guidance_scale))[:, None] * (e[0] - u)
+    for k in range(K):
+        acc = acc + (wk[k] * scales[:, k, None, None])[:, None] * (e[k + 1] - u)
+    return acc
+
+
 def _fold_context(cond, uncond, n_images, device, negative_strength=1.0):
     """Build the single dict of a folded call: rows [cond x n, uncond x n]. `cond` / `uncond`: one dict, or one dict per
     image (paint_with_words_batch: per-image prompts and color maps). Per-image weight maps are stacked to
@@ -105,10 +173,7 @@ def _fold_context(cond, uncond, n_images, device, negative_strength=1.0):
     shared = all(c is conds[0] for c in conds)
 
     def rows(dicts):
-        if all(d is dicts[0] for d in dicts):
-            t = dicts[0]["CONTEXT_TENSOR"]
-            return t.expand(n_images, -1, -1) if t.shape[0] == 1 else t
-        return torch.cat([d["CONTEXT_TENSOR"] for d in dicts], dim=0)
+        return _context_rows(dicts, n_images)
 
     folded = conds[0].copy() if isinstance(conds[0], PwWContext) else PwWContext(conds[0])      # (keeps a pending ORIG map pending)
     folded[KV_CACHE] = {}
@@ -353,8 +418,10 @@ class PwWSampler:
 
     @torch.no_grad()
     def sample(self, cond, uncond, latents, timesteps, guidance_scale, weight_function, extra_channels=None,
-               on_step=None, negative_strength=1.0):
+               on_step=None, negative_strength=1.0, regions=None):
         """cond / uncond: the two context dicts of the PwW protocol, or one dict per image (per-image prompts / maps).
+        regions: None, or the region prompts of the request -- one plan of conditioning.encode_region_prompts or one per image: K more rows
+        per image, blended per latent pixel (ops.region_combine) where guidance is combined otherwise.
         An unconditional dict that carries weight maps (negative regions) is evaluated with `negative_strength * weight_function`.
         latents: [n_images, C, h, w] already scaled by init_noise_sigma (or noised for img2img).
         extra_channels: inpaint's cat([mask, masked_image_latents]) ([n or 1, 5, h, w]) or None."""
@@ -364,33 +431,43 @@ class PwWSampler:
         n = latents.shape[0]
         udt = unet.dtype if hasattr(unet, "dtype") else next(unet.parameters()).dtype
         conds, unconds = _as_list(cond, n), _as_list(uncond, n)
+        blend = None
+        if regions is not None:
+            if any(_has_negative_maps(u) for u in unconds):
+                raise ValueError("region prompts do not combine with negative regions")
+            plans = _as_list(regions, n)
+            if any(tuple(p["masks"].shape[-2:]) != tuple(latents.shape[-2:]) for p in plans):
+                raise ValueError("region prompts: the color map gives %s region masks but the latent is %s: the color map must be 8 x the latent's size"
+                                 % (sorted({tuple(p["masks"].shape[-2:]) for p in plans}), tuple(latents.shape[-2:])))
+            stack = lambda key: torch.stack([p[key] for p in plans], dim=0).to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
+            blend = {"plans": plans, "K": len(plans[0]["contexts"]), "masks": stack("masks"), "weights": stack("weights"), "scales": stack("scales")}
         if self.mode == "eager":   # per-request caches of the fused K|V projections (prompt constant over the steps)
-            for d in conds + unconds:
+            for d in conds + unconds + ([c for p in blend["plans"] for c in p["contexts"]] if blend else []):
                 d.setdefault(KV_CACHE, {}).clear()
         folded = None
         rec = attnmaps.active()        # pww_hip.record_attention_maps(): the recorder rides in the conditional context(s) of this request
         if self.mode != "eager":
-            folded = _fold_context(cond, uncond, n, dev, negative_strength)
+            folded = _fold_context(cond, uncond, n, dev, negative_strength) if blend is None else _fold_regions(cond, regions, uncond, n, dev)
             if self._graphed is not None:
                 folded = self._static_context(folded, weight_function, latents, timesteps, rec)
         if extra_channels is not None and extra_channels.shape[0] != n:
             extra_channels = extra_channels.expand(n, -1, -1, -1)
         if rec is None:
-            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, None, negative_strength)
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, None, negative_strength, blend)
         static = self._static_maps if self._graphed is not None else None
         rec.begin_request(n, latents.shape[-2:], static=static)      # (hipGraph mode: zeroes the static accumulators, before the first replay)
         holders = conds if folded is None else [folded]
         for d in holders:
             d[ATTN_RECORDER] = rec
         try:
-            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength)
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength, blend)
         finally:
             for d in holders:
                 d.pop(ATTN_RECORDER, None)
             rec.end_request(static=static is not None)
 
-    def _denoise(self, conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength=1.0):
-        """The loop of sample() (reference :470-506)."""
+    def _denoise(self, conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength=1.0, blend=None):
+        """The loop of sample() (reference :470-506). blend: the region prompts of the request (sample()), or None."""
         sch, unet, n = self.scheduler, self.unet, latents.shape[0]
         udt = unet.dtype if hasattr(unet, "dtype") else next(unet.parameters()).dtype
         zero_function = lambda w, sigma, qk: 0.0      # noqa: E731  (the reference's unconditional pass, :493)
@@ -398,24 +475,30 @@ class PwWSampler:
         negative_function = lambda w, sigma, qk: ns * weight_function(w, sigma, qk)      # noqa: E731
         # eager mode: per image, what its unconditional dict is evaluated with (one with weight maps of its own: negative regions)
         uncond_functions = [negative_function if _has_negative_maps(u) else zero_function for u in unconds] if folded is None else None
+        K = blend["K"] if blend is not None else 0
         for i, t in enumerate(timesteps):
             sigma, _ = self._sigma_and_index(i, t)
             x = sch.scale_model_input(latents, t)
             if extra_channels is not None:
                 x = torch.cat([x, extra_channels.to(x.dtype)], dim=1)
             if self.mode == "eager":
-                eps_c, eps_u = [], []
+                eps_c, eps_u, eps_r = [], [], [[] for _ in range(K)]
                 for j in range(n):   # the reference is batch-1 (:445); images are independent
                     conds[j].update({"SIGMA": sigma, "WEIGHT_FUNCTION": weight_function})
                     if rec is not None:
                         rec.row = j
                     eps_c.append(unet(x[j:j + 1], t, encoder_hidden_states=conds[j]).sample)
+                    for k in range(K):     # the region prompts: plain cross-attention, like the unconditional pass
+                        ctx = blend["plans"][j]["contexts"][k]
+                        ctx.update({"SIGMA": sigma, "WEIGHT_FUNCTION": zero_function})
+                        eps_r[k].append(unet(x[j:j + 1], t, encoder_hidden_states=ctx).sample)
                     unconds[j].update({"SIGMA": sigma, "WEIGHT_FUNCTION": uncond_functions[j]})
                     eps_u.append(unet(x[j:j + 1], t, encoder_hidden_states=unconds[j]).sample)
                 eps_c, eps_u = torch.cat(eps_c), torch.cat(eps_u)
+                out = torch.cat([eps_c] + [torch.cat(r) for r in eps_r] + [eps_u]) if K else None
             else:
                 folded.update({"SIGMA": sigma, "WEIGHT_FUNCTION": weight_function})
-                x2 = torch.cat([x, x], dim=0).to(udt)
+                x2 = torch.cat([x] * (K + 2), dim=0).to(udt)
                 if self.mode == "graph":
                     slots = folded[COEFF_SLOTS]
                     if not slots.unsupported and not slots.update(weight_function, sigma):
@@ -426,7 +509,11 @@ class PwWSampler:
                 else:
                     out = unet(x2, t, encoder_hidden_states=folded).sample
                 eps_c, eps_u = out[:n], out[n:]
-            if eps_c.dtype in (torch.float16, torch.bfloat16):
+            if K:
+                # rows [base x n, region 1 x n, ..., uncond x n] -> fp32 [n, C, h, w], one launch; outside the captured graph in hipGraph mode
+                combine = ops.region_combine if out.dtype in (torch.float16, torch.bfloat16) else region_blend_fp32
+                noise_pred = combine(out, blend["masks"], blend["weights"], blend["scales"], guidance_scale)
+            elif eps_c.dtype in (torch.float16, torch.bfloat16):
                 noise_pred = ops.cfg_combine(eps_c, eps_u, guidance_scale)     # fp32, :501-503
             else:
                 noise_pred = eps_u + guidance_scale * (eps_c - eps_u)
