@@ -4,24 +4,19 @@ No torch headers are involved: the library is plain HIP behind the C ABI of incl
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
 Six libraries come out of the same sources:
-  libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`, and all that
-                              __graft_entry__.build() compiles.
+  libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
                               measured and not made a default (include/pww_hip.h, section "experiments"). Built by the tests / tools that
                               need it (`build_experiments()`, `python build.py --experiments`), never loaded by the product.
-  libpww_hip_long.so          the cross-attention launches of prompts longer than 77 tokens (128 < M <= 256 keys; include/pww_hip_long.h):
-                              one translation unit over the same csrc/ headers, its own entry points (pww_long_*), loaded by the package on
-                              the first long-prompt call. `build_long()`; __graft_entry__.build() compiles it beside the product library.
-  libpww_hip_scope.so         cross-attention whose bias coefficient is a per-head or per-row score statistic (M <= 128 keys;
-                              include/pww_hip_scope.h): one translation unit over the same csrc/ headers, its own entry points (pww_scope_*),
-                              loaded by the package on the first call of such a weight function. `build_scope()`; __graft_entry__.build()
-                              compiles it beside the other two.
-  libpww_hip_linear.so        linear layers with a bias / residual / GEGLU epilogue (include/pww_hip_linear.h): one translation unit, its own
-                              entry points (pww_linear_*), loaded by the package on the first such call. `build_linear()`;
-                              __graft_entry__.build() compiles it beside the other three.
-  libpww_hip_regions.so       region prompts (include/pww_hip_regions.h): the region masks at latent resolution and the per-pixel blend of
-                              the noise predictions, one translation unit, its own entry points (pww_regions_*), loaded by the package on
-                              the first call that carries region prompts. `build_regions()`; __graft_entry__.build() compiles it too.
+  libpww_hip_<name>.so        the side libraries, one per entry of SIDE_LIBS: one translation unit csrc/pww_<name>.hip over the same csrc/
+                              headers (its host plumbing is pww_side_host.h), its own entry points pww_<name>_* declared in
+                              include/pww_hip_<name>.h and the only visible symbols, loaded by the package on the first call that needs
+                              them (pww_hip/_lib.py, `load_side(name)`). `build_side(name)`, or the aliases `build_long()` ...
+                              `build_regions()`; __graft_entry__.build() compiles all of them beside the product library.
+                                long      the cross-attention launches of prompts longer than 77 tokens (128 < M <= 256 keys)
+                                scope     cross-attention whose bias coefficient is a per-head or per-row score statistic (M <= 128 keys)
+                                linear    linear layers with a bias / residual / GEGLU epilogue
+                                regions   region prompts: the region masks at latent resolution and the per-pixel blend of the noise predictions
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -34,10 +29,6 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "pww_hip", "libpww_hip.so")
 LIB_EXPERIMENTS = os.path.join(HERE, "pww_hip", "libpww_hip_experiments.so")
-LIB_LONG = os.path.join(HERE, "pww_hip", "libpww_hip_long.so")
-LIB_SCOPE = os.path.join(HERE, "pww_hip", "libpww_hip_scope.so")
-LIB_LINEAR = os.path.join(HERE, "pww_hip", "libpww_hip_linear.so")
-LIB_REGIONS = os.path.join(HERE, "pww_hip", "libpww_hip_regions.so")
 # (source, extra defines, object suffix): the instantiation units are compiled once per slice
 UNITS = [("pww_api.hip", [], ""), ("pww_attn.hip", [], ""), ("pww_cross.hip", [], ""), ("pww_cross_lean.hip", [], ""), ("pww_reduce.hip", [], ""),
          ("pww_mask.hip", [], ""), ("pww_qproj.hip", [], ""), ("pww_norm.hip", [], ""), ("pww_blocks.hip", [], ""), ("pww_conv.hip", [], ""), ("pww_probs.hip", [], ""),
@@ -45,16 +36,21 @@ UNITS = [("pww_api.hip", [], ""), ("pww_attn.hip", [], ""), ("pww_cross.hip", []
          ("pww_cross_inst.hip", ["-DPWW_INST_F16", "-DPWW_INST_NW=2"], ".f16.nw2"), ("pww_cross_inst.hip", ["-DPWW_INST_F16", "-DPWW_INST_NW=4"], ".f16.nw4"),
          ("pww_cross_inst.hip", ["-DPWW_INST_BF16", "-DPWW_INST_NW=2"], ".bf16.nw2"), ("pww_cross_inst.hip", ["-DPWW_INST_BF16", "-DPWW_INST_NW=4"], ".bf16.nw4")]
 EXPERIMENT_UNITS = [("pww_cross_out.hip", [], "")]      # sources only the experiments library has
-LONG_UNITS = [("pww_long.hip", ["-fvisibility=hidden"], "")]     # only the pww_long_* entry points are visible: a program may link both libraries
-LONG_HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_cross_tile.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_long.h")]
-SCOPE_UNITS = [("pww_scope.hip", ["-fvisibility=hidden"], "")]   # only the pww_scope_* entry points are visible
-SCOPE_HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_cross_tile.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_scope.h")]
-LINEAR_UNITS = [("pww_linear.hip", ["-fvisibility=hidden"], "")]  # only the pww_linear_* entry points are visible
-LINEAR_HEADERS = ["pww_common.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_linear.h")]
-REGIONS_UNITS = [("pww_regions.hip", ["-fvisibility=hidden"], "")]  # only the pww_regions_* entry points are visible
-REGIONS_HEADERS = ["pww_common.h", os.path.join(REPO, "include", "pww_hip.h"), os.path.join(REPO, "include", "pww_hip_regions.h")]
+_ATTN_HEADERS = ["pww_tile.h", "pww_attn_core.h", "pww_cross_tile.h"]
+# the side libraries: name -> (translation unit, csrc/ headers besides pww_common.h and pww_side_host.h, what it is). Each is
+# pww_hip/libpww_hip_<name>.so behind include/pww_hip_<name>.h, compiled with -fvisibility=hidden: only its pww_<name>_* entry points are
+# visible, so a program may link several of them beside the product library.
+SIDE_FLAGS = ["-fvisibility=hidden"]
+SIDE_LIBS = {
+    "long": ("pww_long.hip", _ATTN_HEADERS, "the long-prompt launches"),
+    "scope": ("pww_scope.hip", _ATTN_HEADERS, "cross-attention with per-head / per-row score statistics"),
+    "linear": ("pww_linear.hip", [], "linear layers with a bias / residual / GEGLU epilogue"),
+    "regions": ("pww_regions.hip", [], "region masks and the per-pixel blend of the noise predictions"),
+}
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
 HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_attn_kernel.h", "pww_cross_tile.h", "pww_cross_kernel.h", os.path.join(REPO, "include", "pww_hip.h")]
+LIB_LONG, LIB_SCOPE, LIB_LINEAR, LIB_REGIONS = (os.path.join(HERE, "pww_hip", "libpww_hip_%s.so" % n) for n in SIDE_LIBS)
+LONG_UNITS, SCOPE_UNITS, LINEAR_UNITS, REGIONS_UNITS = ([(v[0], SIDE_FLAGS, "")] for v in SIDE_LIBS.values())     # (as in UNITS)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
 # into SGPRs by the dispatcher instead of fetched by the wave's first s_load (gfx950 supports kernarg preload; the compiler keeps a compatibility
@@ -82,7 +78,8 @@ def _build(lib, units, defines, objdir, verbose, jobs=None):
     os.makedirs(objdir, exist_ok=True)
     # longest compiles first (the general cross-attention slices), at most `jobs` at a time
     order = sorted(units, key=lambda u: {"pww_cross_inst.hip": 0, "pww_attn_inst.hip": 1, "pww_cross_lean.hip": 2}.get(u[0], 3))
-    jobs = jobs or max(2, min(len(order), (os.cpu_count() or 4)))
+    # (a shared build box reports far more CPUs than one build may use: MAX_JOBS, or 16)
+    jobs = jobs or max(2, min(len(order), os.cpu_count() or 4, int(os.environ.get("MAX_JOBS", 16))))
     pending, running, objs = list(order), [], []
     while pending or running:
         while pending and len(running) < jobs:
@@ -120,36 +117,20 @@ def build_experiments(force=False, verbose=False):
     return _build(LIB_EXPERIMENTS, UNITS + EXPERIMENT_UNITS, ["-DPWW_EXPERIMENTS=1"], os.path.join(HERE, "build", "experiments"), verbose)
 
 
-def build_long(force=False, verbose=False):
-    """libpww_hip_long.so: the long-prompt launches (include/pww_hip_long.h)."""
-    deps = [os.path.join(CSRC, u[0]) for u in LONG_UNITS] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in LONG_HEADERS] + [__file__]
-    if not force and not _newer(LIB_LONG, deps):
-        return LIB_LONG
-    return _build(LIB_LONG, LONG_UNITS, [], os.path.join(HERE, "build", "long"), verbose)
+def build_side(name, force=False, verbose=False):
+    """libpww_hip_<name>.so, one of SIDE_LIBS (include/pww_hip_<name>.h)."""
+    unit, headers, _ = SIDE_LIBS[name]
+    lib = os.path.join(HERE, "pww_hip", "libpww_hip_%s.so" % name)
+    deps = [os.path.join(CSRC, f) for f in [unit, "pww_common.h", "pww_side_host.h"] + headers] + [os.path.join(REPO, "include", h) for h in ("pww_hip.h", "pww_hip_%s.h" % name)] + [__file__]
+    if not force and not _newer(lib, deps):
+        return lib
+    return _build(lib, [(unit, SIDE_FLAGS, "")], [], os.path.join(HERE, "build", name), verbose)
 
 
-def build_scope(force=False, verbose=False):
-    """libpww_hip_scope.so: cross-attention with per-head / per-row score statistics (include/pww_hip_scope.h)."""
-    deps = [os.path.join(CSRC, u[0]) for u in SCOPE_UNITS] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in SCOPE_HEADERS] + [__file__]
-    if not force and not _newer(LIB_SCOPE, deps):
-        return LIB_SCOPE
-    return _build(LIB_SCOPE, SCOPE_UNITS, [], os.path.join(HERE, "build", "scope"), verbose)
-
-
-def build_linear(force=False, verbose=False):
-    """libpww_hip_linear.so: linear layers with a bias / residual / GEGLU epilogue (include/pww_hip_linear.h)."""
-    deps = [os.path.join(CSRC, u[0]) for u in LINEAR_UNITS] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in LINEAR_HEADERS] + [__file__]
-    if not force and not _newer(LIB_LINEAR, deps):
-        return LIB_LINEAR
-    return _build(LIB_LINEAR, LINEAR_UNITS, [], os.path.join(HERE, "build", "linear"), verbose)
-
-
-def build_regions(force=False, verbose=False):
-    """libpww_hip_regions.so: region masks and the per-pixel blend of the noise predictions (include/pww_hip_regions.h)."""
-    deps = [os.path.join(CSRC, u[0]) for u in REGIONS_UNITS] + [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in REGIONS_HEADERS] + [__file__]
-    if not force and not _newer(LIB_REGIONS, deps):
-        return LIB_REGIONS
-    return _build(LIB_REGIONS, REGIONS_UNITS, [], os.path.join(HERE, "build", "regions"), verbose)
+def build_long(force=False, verbose=False): return build_side("long", force, verbose)  # noqa: E704
+def build_scope(force=False, verbose=False): return build_side("scope", force, verbose)  # noqa: E704
+def build_linear(force=False, verbose=False): return build_side("linear", force, verbose)  # noqa: E704
+def build_regions(force=False, verbose=False): return build_side("regions", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):
@@ -176,10 +157,8 @@ if __name__ == "__main__":
     force = "--force" in sys.argv
     print(build_lib(force=force, verbose=True))
     print(build_native_check(force=force))
-    print(build_long(force=force, verbose=True))
-    print(build_scope(force=force, verbose=True))
-    print(build_linear(force=force, verbose=True))
-    print(build_regions(force=force, verbose=True))
+    for name in SIDE_LIBS:
+        print(build_side(name, force=force, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=force, verbose=True))
         print(build_native_check_experiments(force=force))

@@ -156,19 +156,6 @@ int qk_parts_count(const pww_attn_desc_t *d) {
     return n > 0x7fffffffL ? 0 : (int)n;
 }
 
-static int stat_fields(int stat_kind) {
-    switch (stat_kind) {
-        case PWW_STAT_NONE: return 0;
-        case PWW_STAT_MAX: return 1;
-        case PWW_STAT_MIN: return 2;
-        case PWW_STAT_ABSMAX: return 3;
-        case PWW_STAT_MEAN: return 4;
-        case PWW_STAT_STD: return 12;
-        case PWW_STAT_ALL: return 15;
-        default: return -1;
-    }
-}
-
 int qk_parts(const void *q, const void *k, const float *gate, const pww_attn_desc_t *d, int stat_kind, int gated_images, double *partials,
              size_t partials_bytes, hipStream_t stream) {
     if (!q || !k || !d || !partials) { set_error("qk_parts: null argument"); return PWW_EINVAL; }

@@ -20,6 +20,21 @@ __device__ __forceinline__ void load_q_frags_buf(typename Vec<T>::v8 (&qf)[KS], 
     }
 }
 
+// host: the fields of the partials a statistic selector needs (bit 0 max, 1 min, 2 sum, 3 sum of squares); 0 for PWW_STAT_NONE, -1 for an
+// unknown selector
+inline int stat_fields(int stat_kind) {
+    switch (stat_kind) {
+        case PWW_STAT_NONE: return 0;
+        case PWW_STAT_MAX: return 1;
+        case PWW_STAT_MIN: return 2;
+        case PWW_STAT_ABSMAX: return 3;
+        case PWW_STAT_MEAN: return 4;
+        case PWW_STAT_STD: return 12;
+        case PWW_STAT_ALL: return 15;
+        default: return -1;
+    }
+}
+
 // ---- the score statistic's partials at kernel entry (pww_cross_out.hip; pww_cross_lean.hip carries the same steps inline) -----------------
 // [B][nparts][4] fp64 { max, min, sum, sum of squares }: lane i of EVERY wave requests partials i, i + 64, ... (PARTS_UNROLL per lane from
 // the prologue's load batch) and folds them with shuffles -- the same order in every wave of every workgroup, no LDS, no barrier.

@@ -22,46 +22,15 @@
 // Split-K: each workgroup writes its fp32 partial tile to a caller-owned workspace ([split][M][N]), a second launch folds the partials in
 // split order and applies the same epilogue (GEGLU included). No atomics, no inter-workgroup waits: bitwise repeatable.
 //
-// Built as a library of its own (libpww_hip_linear.so, include/pww_hip_linear.h): the unit is self-contained, brings its own error slot, and only
-// the pww_linear_* entry points are visible (compiled with -fvisibility=hidden).
-#include <string.h>
-#include "pww_common.h"
+// Built as a library of its own (libpww_hip_linear.so, include/pww_hip_linear.h): the unit is self-contained, its host plumbing is pww_side_host.h, and
+// only the pww_linear_* entry points are visible (compiled with -fvisibility=hidden).
+#define PWW_SIDE_LIB "libpww_hip_linear"
+#include "pww_side_host.h"
 #include "../../include/pww_hip_linear.h"
 
 #define PWW_LINEAR_API extern "C" __attribute__((visibility("default")))
 
 namespace pww {
-
-// ---- host plumbing of this library ---------------------------------------------------------------------------------------------------
-static thread_local char g_linear_err[512] = "";
-
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_linear_err, sizeof(g_linear_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_hip(hipError_t e, const char *what) {
-    if (e == hipSuccess) return PWW_OK;
-    set_error("%s: %s (%s)", what, hipGetErrorString(e), hipGetErrorName(e));
-    return PWW_EHIP;
-}
-
-bool arch_ok() {
-    static thread_local int cached = -1;
-    if (cached < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (check_hip(hipGetDevice(&dev), "hipGetDevice") || check_hip(hipGetDeviceProperties(&prop, dev), "hipGetDeviceProperties")) return false;
-        cached = strncmp(prop.gcnArchName, "gfx950", 6) == 0 && (prop.gcnArchName[6] == 0 || prop.gcnArchName[6] == ':') ? 1 : 0;
-    }
-    if (!cached) set_error("libpww_hip_linear is built for gfx950 (MI355X) only");
-    return cached == 1;
-}
-
-// (this library has no timing slot: its launches are timed with event pairs or a profiler)
-bool profile_take(hipEvent_t *, hipEvent_t *, hipStream_t) { return false; }
 
 namespace {
 
@@ -390,7 +359,7 @@ int linear_fwd(const void *x, const void *w, const void *bias, const void *resid
 }  // namespace pww
 
 PWW_LINEAR_API int pww_linear_version(void) { return PWW_LINEAR_VERSION; }
-PWW_LINEAR_API const char *pww_linear_last_error(void) { return pww::g_linear_err; }
+PWW_LINEAR_API const char *pww_linear_last_error(void) { return pww::last_error(); }
 PWW_LINEAR_API size_t pww_linear_workspace_bytes(const pww_linear_desc_t *desc) { return pww::linear_workspace_bytes(desc); }
 PWW_LINEAR_API int pww_linear_fwd(const void *x, const void *w, const void *bias, const void *residual, void *y, const pww_linear_desc_t *desc,
                                   void *workspace, size_t workspace_bytes, void *stream) {

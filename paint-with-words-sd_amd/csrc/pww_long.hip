@@ -13,10 +13,12 @@
 //
 // Traffic and arithmetic per launch against the chip's rates: DESIGN.md section 4, K8 (the one place that states them).
 //
-// This unit carries its own copies of the few host helpers pww_common.h declares (error text, timing slot): nothing is shared with
+// The host helpers pww_common.h declares are this library's own (pww_side_host.h; the timing slot is below): nothing is shared with
 // libpww_hip.so at link time, and only the pww_long_* entry points are visible (the unit is compiled with -fvisibility=hidden).
-#include <string.h>
 #include <mutex>
+#define PWW_SIDE_LIB "libpww_hip_long"
+#define PWW_SIDE_OWN_PROFILE
+#include "pww_side_host.h"
 #include "pww_attn_core.h"
 #include "pww_cross_tile.h"
 #include "../../include/pww_hip_long.h"
@@ -24,34 +26,6 @@
 #define PWW_LONG_API extern "C" __attribute__((visibility("default")))
 
 namespace pww {
-
-// ---- host plumbing of this library ---------------------------------------------------------------------------------------------------
-static thread_local char g_long_err[512] = "";
-
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_long_err, sizeof(g_long_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_hip(hipError_t e, const char *what) {
-    if (e == hipSuccess) return PWW_OK;
-    set_error("%s: %s (%s)", what, hipGetErrorString(e), hipGetErrorName(e));
-    return PWW_EHIP;
-}
-
-bool arch_ok() {
-    static thread_local int cached = -1;
-    if (cached < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (check_hip(hipGetDevice(&dev), "hipGetDevice") || check_hip(hipGetDeviceProperties(&prop, dev), "hipGetDeviceProperties")) return false;
-        cached = strncmp(prop.gcnArchName, "gfx950", 6) == 0 && (prop.gcnArchName[6] == 0 || prop.gcnArchName[6] == ':') ? 1 : 0;
-    }
-    if (!cached) set_error("libpww_hip_long is built for gfx950 (MI355X) only");
-    return cached == 1;
-}
 
 // one timing slot (pww_long_profile_*): the event pair goes to the next launch of the arming thread
 static std::mutex g_long_prof_mutex;
@@ -219,21 +193,6 @@ static int long_qk_parts_count(const pww_attn_desc_t *d) {
     const long n = lqk_plan(d).nparts;
     return n > 0x7fffffffL ? 0 : (int)n;
 }
-
-static int stat_fields(int stat_kind) {
-    switch (stat_kind) {
-        case PWW_STAT_NONE: return 0;
-        case PWW_STAT_MAX: return 1;
-        case PWW_STAT_MIN: return 2;
-        case PWW_STAT_ABSMAX: return 3;
-        case PWW_STAT_MEAN: return 4;
-        case PWW_STAT_STD: return 12;
-        case PWW_STAT_ALL: return 15;
-        default: return -1;
-    }
-}
-
-static bool aligned16(const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
 
 static int long_qk_parts(const void *q, const void *k, const float *gate, const pww_attn_desc_t *d, int stat_kind, int gated_images, double *partials,
                          size_t partials_bytes, hipStream_t stream) {
@@ -826,7 +785,7 @@ static int long_probs(const void *q, const void *k, const float *bias, const dou
 }  // namespace pww
 
 PWW_LONG_API int pww_long_version(void) { return PWW_LONG_VERSION; }
-PWW_LONG_API const char *pww_long_last_error(void) { return pww::g_long_err; }
+PWW_LONG_API const char *pww_long_last_error(void) { return pww::last_error(); }
 
 PWW_LONG_API int pww_long_qk_parts(const void *q, const void *k, const float *gate, const pww_attn_desc_t *desc, int32_t stat_kind, int32_t gated_images,
                                    double *partials, size_t partials_bytes, void *stream) {

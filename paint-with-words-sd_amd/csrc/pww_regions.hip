@@ -14,44 +14,16 @@
 // The arithmetic is fp32, one IEEE operation per step in the order include/pww_hip_regions.h writes down; the unit is compiled with
 // -ffp-contract=off (build.py PER_FILE_FLAGS) and spells the operations as __f*_rn besides, so a CPU restatement matches bit for bit.
 //
-// Built as a library of its own (libpww_hip_regions.so): the unit is self-contained, brings its own error slot, and only the pww_regions_*
-// entry points are visible (compiled with -fvisibility=hidden).
+// Built as a library of its own (libpww_hip_regions.so): the unit is self-contained, its host plumbing is pww_side_host.h, and only the
+// pww_regions_* entry points are visible (compiled with -fvisibility=hidden).
 #include <math.h>
-#include <string.h>
-#include "pww_common.h"
+#define PWW_SIDE_LIB "libpww_hip_regions"
+#include "pww_side_host.h"
 #include "../../include/pww_hip_regions.h"
 
 #define PWW_REGIONS_API extern "C" __attribute__((visibility("default")))
 
 namespace pww {
-
-// ---- host plumbing of this library ---------------------------------------------------------------------------------------------------
-static thread_local char g_regions_err[512] = "";
-
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_regions_err, sizeof(g_regions_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_hip(hipError_t e, const char *what) {
-    if (e == hipSuccess) return PWW_OK;
-    set_error("%s: %s (%s)", what, hipGetErrorString(e), hipGetErrorName(e));
-    return PWW_EHIP;
-}
-
-bool arch_ok() {
-    static thread_local int cached = -1;
-    if (cached < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (check_hip(hipGetDevice(&dev), "hipGetDevice") || check_hip(hipGetDeviceProperties(&prop, dev), "hipGetDeviceProperties")) return false;
-        cached = strncmp(prop.gcnArchName, "gfx950", 6) == 0 && (prop.gcnArchName[6] == 0 || prop.gcnArchName[6] == ':') ? 1 : 0;
-    }
-    if (!cached) set_error("libpww_hip_regions is built for gfx950 (MI355X) only");
-    return cached == 1;
-}
 
 namespace {
 
@@ -261,7 +233,7 @@ int regions_combine(const void *eps, const float *masks, const float *weights, c
 }  // namespace pww
 
 PWW_REGIONS_API int pww_regions_version(void) { return PWW_REGIONS_VERSION; }
-PWW_REGIONS_API const char *pww_regions_last_error(void) { return pww::g_regions_err; }
+PWW_REGIONS_API const char *pww_regions_last_error(void) { return pww::last_error(); }
 PWW_REGIONS_API int pww_regions_masks(const void *rgb, int32_t H, int32_t W, const uint8_t *colors, int32_t K, float feather, float *out, void *stream) {
     return pww::regions_masks(rgb, H, W, colors, K, feather, out, static_cast<hipStream_t>(stream));
 }

@@ -16,9 +16,10 @@
 //                             The bias row of a lane is read from global memory where the lane needs it (8 consecutive keys = two
 //                             16-byte buffer loads per 16-key group), requested before the statistic is reduced.
 //
-// This unit carries its own copies of the few host helpers pww_common.h declares: nothing is shared with libpww_hip.so at link time,
+// The host helpers pww_common.h declares are this library's own (pww_side_host.h): nothing is shared with libpww_hip.so at link time,
 // and only the pww_scope_* entry points are visible (the unit is compiled with -fvisibility=hidden).
-#include <string.h>
+#define PWW_SIDE_LIB "libpww_hip_scope"
+#include "pww_side_host.h"
 #include "pww_attn_core.h"
 #include "pww_cross_tile.h"
 #include "../../include/pww_hip_scope.h"
@@ -26,37 +27,6 @@
 #define PWW_SCOPE_API extern "C" __attribute__((visibility("default")))
 
 namespace pww {
-
-// ---- host plumbing of this library ---------------------------------------------------------------------------------------------------
-static thread_local char g_scope_err[512] = "";
-
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_scope_err, sizeof(g_scope_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_hip(hipError_t e, const char *what) {
-    if (e == hipSuccess) return PWW_OK;
-    set_error("%s: %s (%s)", what, hipGetErrorString(e), hipGetErrorName(e));
-    return PWW_EHIP;
-}
-
-bool arch_ok() {
-    static thread_local int cached = -1;
-    if (cached < 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (check_hip(hipGetDevice(&dev), "hipGetDevice") || check_hip(hipGetDeviceProperties(&prop, dev), "hipGetDeviceProperties")) return false;
-        cached = strncmp(prop.gcnArchName, "gfx950", 6) == 0 && (prop.gcnArchName[6] == 0 || prop.gcnArchName[6] == ':') ? 1 : 0;
-    }
-    if (!cached) set_error("libpww_hip_scope is built for gfx950 (MI355X) only");
-    return cached == 1;
-}
-
-// (this library has no timing slot: its launches are timed with event pairs or a profiler)
-bool profile_take(hipEvent_t *, hipEvent_t *, hipStream_t) { return false; }
 
 constexpr int SCOPE_NW = 4;               // waves per workgroup, 32 query rows each
 constexpr int SCOPE_KB = 4;               // 32-key blocks at most (M <= 128)
@@ -159,18 +129,8 @@ static int head_parts_count(const pww_attn_desc_t *d) {
     return (int)((nrb + per - 1) / per);
 }
 
-static int stat_fields(int stat_kind) {
-    switch (stat_kind) {
-        case PWW_STAT_MAX: return 1;
-        case PWW_STAT_MIN: return 2;
-        case PWW_STAT_ABSMAX: return 3;
-        case PWW_STAT_MEAN: return 4;
-        case PWW_STAT_STD: return 12;
-        default: return -1;
-    }
-}
-
-static bool aligned16(const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
+// the fields of ONE statistic: this library takes neither PWW_STAT_NONE nor PWW_STAT_ALL (the selector is checked before stat_fields sees it)
+static int stat_fields_one(int stat_kind) { return stat_kind == PWW_STAT_NONE || stat_kind == PWW_STAT_ALL ? -1 : stat_fields(stat_kind); }
 
 // what both entry points ask of the descriptor's q / k side
 static int check_qk(const char *me, const pww_attn_desc_t *d) {
@@ -197,7 +157,7 @@ static int scope_head_parts(const void *q, const void *k, const float *gate, con
     const char *me = "pww_scope_head_parts";
     if (!q || !k || !d || !partials) { set_error("%s: null argument", me); return PWW_EINVAL; }
     if (int rc = check_qk(me, d)) return rc;
-    const int fields = stat_fields(stat_kind);
+    const int fields = stat_fields_one(stat_kind);
     if (fields <= 0) { set_error("%s: bad statistic selector %d", me, stat_kind); return PWW_EINVAL; }
     if (!aligned16(q) || !aligned16(k) || !aligned16(partials) || (reinterpret_cast<uintptr_t>(gate) & 3)) {
         set_error("%s: q, k and partials must be 16-byte aligned, gate 4-byte", me);
@@ -516,7 +476,7 @@ static int scope_cross_attn(const void *q, const void *k, const void *v, void *o
     }
     if (int rc = check_qk(me, d)) return rc;
     if (scope != PWW_SCOPE_HEAD && scope != PWW_SCOPE_ROW) { set_error("%s: bad scope %d (PWW_SCOPE_HEAD / PWW_SCOPE_ROW)", me, scope); return PWW_EINVAL; }
-    if (stat_fields(stat_kind) <= 0) { set_error("%s: bad statistic selector %d", me, stat_kind); return PWW_EINVAL; }
+    if (stat_fields_one(stat_kind) <= 0) { set_error("%s: bad statistic selector %d", me, stat_kind); return PWW_EINVAL; }
     if (stat_kind == PWW_STAT_STD && (scope == PWW_SCOPE_ROW ? d->M : (long)d->N * d->M) < 2) {
         set_error("%s: the standard deviation of a single score is undefined", me);
         return PWW_EINVAL;
@@ -570,7 +530,7 @@ static int scope_cross_attn(const void *q, const void *k, const void *v, void *o
 }  // namespace pww
 
 PWW_SCOPE_API int pww_scope_version(void) { return PWW_SCOPE_VERSION; }
-PWW_SCOPE_API const char *pww_scope_last_error(void) { return pww::g_scope_err; }
+PWW_SCOPE_API const char *pww_scope_last_error(void) { return pww::last_error(); }
 
 PWW_SCOPE_API int32_t pww_scope_head_parts_count(const pww_attn_desc_t *desc) { return pww::head_parts_count(desc); }
 

@@ -12,18 +12,14 @@ LIB_PATH = os.environ.get("PWW_HIP_LIB", os.path.join(_HERE, "libpww_hip.so"))
 # "experiments"). Tests and A/B tools load it (`load_experiments()`, or a whole process through PWW_HIP_LIB); the product never does.
 EXPERIMENTS_LIB_PATH = os.environ.get("PWW_HIP_EXPERIMENTS_LIB", os.path.join(_HERE, "libpww_hip_experiments.so"))
 
-# the launches of prompts longer than 77 tokens (128 < M <= 256 keys; include/pww_hip_long.h): loaded on the first long-prompt call (`load_long()`)
+# the side libraries (SIDE below; `load_side(name)`), each loaded on the first call that needs it:
+#   long      the launches of prompts longer than 77 tokens (128 < M <= 256 keys; include/pww_hip_long.h)
+#   scope     cross-attention with a per-head / per-row score statistic (M <= 128 keys; include/pww_hip_scope.h)
+#   linear    linear layers with a bias / residual / GEGLU epilogue (include/pww_hip_linear.h): ops.linear
+#   regions   region prompts: the region masks at latent resolution and the per-pixel blend of the noise predictions (include/pww_hip_regions.h)
 LONG_LIB_PATH = os.environ.get("PWW_HIP_LONG_LIB", os.path.join(_HERE, "libpww_hip_long.so"))
-
-# cross-attention with a per-head / per-row score statistic (M <= 128 keys; include/pww_hip_scope.h): loaded on the first call of such a
-# weight function (`load_scope()`)
 SCOPE_LIB_PATH = os.environ.get("PWW_HIP_SCOPE_LIB", os.path.join(_HERE, "libpww_hip_scope.so"))
-
-# linear layers with a bias / residual / GEGLU epilogue (include/pww_hip_linear.h): loaded on the first call of ops.linear (`load_linear()`)
 LINEAR_LIB_PATH = os.environ.get("PWW_HIP_LINEAR_LIB", os.path.join(_HERE, "libpww_hip_linear.so"))
-
-# region prompts: the region masks at latent resolution and the per-pixel blend of the noise predictions (include/pww_hip_regions.h): loaded on
-# the first call that carries region prompts (`load_regions()`)
 REGIONS_LIB_PATH = os.environ.get("PWW_HIP_REGIONS_LIB", os.path.join(_HERE, "libpww_hip_regions.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
@@ -269,142 +265,88 @@ def load_experiments():
     return _exp
 
 
-_long = None
+# ---- the side libraries: libpww_hip_<name>.so behind include/pww_hip_<name>.h, each loaded on the first call that needs it --------------
+_P = ctypes.POINTER
+_vp, _i32, _i64, _f32, _f64, _sz, _int = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_int
+_HINT = "(rebuild: python paint-with-words-sd_amd/build.py, or __graft_entry__.build())"
+# name -> path: the module attribute that holds the file's path (read per call: PWW_HIP_<NAME>_LIB sets it, tests patch it)
+#         exports / min_version: every symbol the header declares, the oldest ABI (pww_<name>_version()) this package drives
+#         missing_ok: a missing file returns None (the caller has another route that computes the same thing) instead of raising
+#         needs: what cannot run without the library (error text)
+#         sigs: entry point -> (argtypes, restype); pww_<name>_version and pww_<name>_last_error are bound by load_side itself
+SIDE = {
+    "long": dict(path="LONG_LIB_PATH", exports=LONG_EXPORTS, min_version=LONG_MIN_VERSION, missing_ok=False, needs="prompts longer than 77 tokens need it", sigs={
+        "pww_long_qk_parts": ([_vp, _vp, _vp, _P(AttnDesc), _i32, _i32, _vp, _sz, _vp], _int),
+        "pww_long_qk_parts_count": ([_P(AttnDesc)], _i32),
+        "pww_long_cross_attn_fwd_parts": ([_vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _P(AttnDesc), _vp, _i32, _vp, _P(CrossOpts), _vp], _int),
+        "pww_long_cross_attn_probs": ([_vp, _vp, _vp, _vp, _i32, _f64, _f32, _vp, _P(AttnDesc), _P(CrossOpts), _vp, _P(ProbsDesc), _vp], _int),
+        "pww_long_profile_arm": ([], _int),
+        "pww_long_profile_elapsed_us": ([_P(_f32)], _int)}),
+    "scope": dict(path="SCOPE_LIB_PATH", exports=SCOPE_EXPORTS, min_version=SCOPE_MIN_VERSION, missing_ok=True, needs="per-head / per-row score statistics need it", sigs={
+        "pww_scope_head_parts_count": ([_P(AttnDesc)], _i32),
+        "pww_scope_head_parts": ([_vp, _vp, _vp, _P(AttnDesc), _i32, _vp, _sz, _vp], _int),
+        "pww_scope_cross_attn_fwd": ([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _P(AttnDesc), _vp, _i32, _vp, _P(CrossOpts), _vp], _int)}),
+    "linear": dict(path="LINEAR_LIB_PATH", exports=LINEAR_EXPORTS, min_version=LINEAR_MIN_VERSION, missing_ok=False, needs="linear layers on the native kernel need it", sigs={
+        "pww_linear_workspace_bytes": ([_P(LinearDesc)], _sz),
+        "pww_linear_fwd": ([_vp, _vp, _vp, _vp, _vp, _P(LinearDesc), _vp, _sz, _vp], _int)}),
+    "regions": dict(path="REGIONS_LIB_PATH", exports=REGIONS_EXPORTS, min_version=REGIONS_MIN_VERSION, missing_ok=False, needs="region prompts need it", sigs={
+        "pww_regions_masks": ([_vp, _i32, _i32, _vp, _i32, _f32, _vp, _vp], _int),
+        "pww_regions_combine": ([_vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i64, _i32, _vp], _int)}),
+}
+_side = {}      # name -> loaded handle
 
 
+def load_side(name):
+    """libpww_hip_<name>.so of SIDE, loaded once. A missing file returns None where the table says so (scope: the caller keeps the
+    materialised route) and raises otherwise -- there is no second implementation to fall back to. A file that is there but stale, broken
+    or short of an entry point raises. Every failure is a PwwHipError with the rebuild hint."""
+    lib = _side.get(name)
+    if lib is not None:
+        return lib
+    spec, path, so, pre = SIDE[name], globals()[SIDE[name]["path"]], "libpww_hip_%s.so" % name, "pww_%s_" % name
+    if not os.path.isfile(path):
+        if spec["missing_ok"]:
+            return None
+        raise PwwHipError("%s not found at %s: %s %s" % (so, path, spec["needs"], _HINT))
+    try:
+        lib = ctypes.CDLL(path)
+        getattr(lib, pre + "version").restype = _int
+        version = getattr(lib, pre + "version")()
+    except (OSError, AttributeError) as e:
+        raise PwwHipError("%s at %s cannot be loaded: %s %s" % (so, path, e, _HINT))
+    # first of all: an older library lacks symbols that are bound below
+    if version // 100 != 1 or version < spec["min_version"]:
+        raise PwwHipError("%s ABI version %d is not 1.x >= %d %s" % (so[:-3], version, spec["min_version"], _HINT))
+    missing = [n for n in spec["exports"] if not hasattr(lib, n)]
+    if missing:
+        raise PwwHipError("%s at %s lacks %s %s" % (so, path, missing, _HINT))
+    for fn, (argtypes, restype) in spec["sigs"].items():
+        getattr(lib, fn).argtypes, getattr(lib, fn).restype = argtypes, restype
+    getattr(lib, pre + "last_error").restype = ctypes.c_char_p
+    lib.pww_last_error = getattr(lib, pre + "last_error")        # (`check(rc, what, lib)` asks the library it is given)
+    _side[name] = lib
+    return lib
+
+
+# the public names (ops.py calls them per launch: after the first call, one lookup and one test)
 def load_long():
-    """libpww_hip_long.so (the cross-attention launches over 129 .. 256 keys), loaded once, on the first long-prompt call. A missing file raises:
-    there is no second implementation to fall back to."""
-    global _long
-    if _long is not None:
-        return _long
-    if not os.path.isfile(LONG_LIB_PATH):
-        raise PwwHipError("libpww_hip_long.so not found at %s: prompts longer than 77 tokens need it. Build it with "
-                          "`python paint-with-words-sd_amd/build.py` (or __graft_entry__.build())." % LONG_LIB_PATH)
-    lib = ctypes.CDLL(LONG_LIB_PATH)
-    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-    lib.pww_long_version.restype = ctypes.c_int
-    if lib.pww_long_version() // 100 != 1 or lib.pww_long_version() < LONG_MIN_VERSION:
-        raise PwwHipError("libpww_hip_long ABI version %d is not 1.x >= %d (rebuild: python paint-with-words-sd_amd/build.py)"
-                          % (lib.pww_long_version(), LONG_MIN_VERSION))
-    lib.pww_long_last_error.restype = ctypes.c_char_p
-    lib.pww_last_error = lib.pww_long_last_error         # (`check(rc, what, lib)` asks the library it is given)
-    lib.pww_long_qk_parts.argtypes = [vp, vp, vp, ctypes.POINTER(AttnDesc), i32, i32, vp, ctypes.c_size_t, vp]
-    lib.pww_long_qk_parts.restype = ctypes.c_int
-    lib.pww_long_qk_parts_count.argtypes = [ctypes.POINTER(AttnDesc)]
-    lib.pww_long_qk_parts_count.restype = ctypes.c_int32
-    lib.pww_long_cross_attn_fwd_parts.argtypes = [vp, vp, vp, vp, vp, i32, f32, vp, ctypes.POINTER(AttnDesc), vp, i32, vp, ctypes.POINTER(CrossOpts), vp]
-    lib.pww_long_cross_attn_fwd_parts.restype = ctypes.c_int
-    lib.pww_long_cross_attn_probs.argtypes = [vp, vp, vp, vp, i32, ctypes.c_double, f32, vp, ctypes.POINTER(AttnDesc), ctypes.POINTER(CrossOpts), vp,
-                                              ctypes.POINTER(ProbsDesc), vp]
-    lib.pww_long_cross_attn_probs.restype = ctypes.c_int
-    lib.pww_long_profile_arm.argtypes = []
-    lib.pww_long_profile_arm.restype = ctypes.c_int
-    lib.pww_long_profile_elapsed_us.argtypes = [ctypes.POINTER(ctypes.c_float)]
-    lib.pww_long_profile_elapsed_us.restype = ctypes.c_int
-    _long = lib
-    return _long
-
-
-_scope = None
+    lib = _side.get("long")
+    return lib if lib is not None else load_side("long")
 
 
 def load_scope():
-    """libpww_hip_scope.so (cross-attention with a per-head / per-row score statistic), loaded once, on the first call that asks for it.
-    Returns None when the file is missing: the caller keeps the materialised route, which computes the same thing. A file that is
-    there but stale or broken raises with the rebuild hint."""
-    global _scope
-    if _scope is not None:
-        return _scope
-    if not os.path.isfile(SCOPE_LIB_PATH):
-        return None
-    hint = "(rebuild: python paint-with-words-sd_amd/build.py)"
-    try:
-        lib = ctypes.CDLL(SCOPE_LIB_PATH)
-        lib.pww_scope_version.restype = ctypes.c_int
-        version = lib.pww_scope_version()
-    except (OSError, AttributeError) as e:
-        raise PwwHipError("libpww_hip_scope.so at %s cannot be loaded: %s %s" % (SCOPE_LIB_PATH, e, hint))
-    if version // 100 != 1 or version < SCOPE_MIN_VERSION:
-        raise PwwHipError("libpww_hip_scope ABI version %d is not 1.x >= %d %s" % (version, SCOPE_MIN_VERSION, hint))
-    missing = [n for n in SCOPE_EXPORTS if not hasattr(lib, n)]
-    if missing:
-        raise PwwHipError("libpww_hip_scope.so at %s lacks %s %s" % (SCOPE_LIB_PATH, missing, hint))
-    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-    lib.pww_scope_last_error.restype = ctypes.c_char_p
-    lib.pww_last_error = lib.pww_scope_last_error        # (`check(rc, what, lib)` asks the library it is given)
-    lib.pww_scope_head_parts_count.argtypes = [ctypes.POINTER(AttnDesc)]
-    lib.pww_scope_head_parts_count.restype = ctypes.c_int32
-    lib.pww_scope_head_parts.argtypes = [vp, vp, vp, ctypes.POINTER(AttnDesc), i32, vp, ctypes.c_size_t, vp]
-    lib.pww_scope_head_parts.restype = ctypes.c_int
-    lib.pww_scope_cross_attn_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, f32, vp, ctypes.POINTER(AttnDesc), vp, i32, vp, ctypes.POINTER(CrossOpts), vp]
-    lib.pww_scope_cross_attn_fwd.restype = ctypes.c_int
-    _scope = lib
-    return _scope
-
-
-_linear = None
+    lib = _side.get("scope")
+    return lib if lib is not None else load_side("scope")
 
 
 def load_linear():
-    """libpww_hip_linear.so (linear layers with a bias / residual / GEGLU epilogue), loaded once, on the first call that asks for it. A
-    missing kernel is an error: a file that is missing, stale or broken raises with the rebuild hint."""
-    global _linear
-    if _linear is not None:
-        return _linear
-    hint = "(rebuild: python paint-with-words-sd_amd/build.py)"
-    try:
-        lib = ctypes.CDLL(LINEAR_LIB_PATH)
-        lib.pww_linear_version.restype = ctypes.c_int
-        version = lib.pww_linear_version()
-    except (OSError, AttributeError) as e:
-        raise PwwHipError("libpww_hip_linear.so at %s cannot be loaded: %s %s" % (LINEAR_LIB_PATH, e, hint))
-    if version // 100 != 1 or version < LINEAR_MIN_VERSION:
-        raise PwwHipError("libpww_hip_linear ABI version %d is not 1.x >= %d %s" % (version, LINEAR_MIN_VERSION, hint))
-    missing = [n for n in LINEAR_EXPORTS if not hasattr(lib, n)]
-    if missing:
-        raise PwwHipError("libpww_hip_linear.so at %s lacks %s %s" % (LINEAR_LIB_PATH, missing, hint))
-    vp = ctypes.c_void_p
-    lib.pww_linear_last_error.restype = ctypes.c_char_p
-    lib.pww_last_error = lib.pww_linear_last_error        # (`check(rc, what, lib)` asks the library it is given)
-    lib.pww_linear_workspace_bytes.argtypes = [ctypes.POINTER(LinearDesc)]
-    lib.pww_linear_workspace_bytes.restype = ctypes.c_size_t
-    lib.pww_linear_fwd.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(LinearDesc), vp, ctypes.c_size_t, vp]
-    lib.pww_linear_fwd.restype = ctypes.c_int
-    _linear = lib
-    return _linear
-
-
-_regions = None
+    lib = _side.get("linear")
+    return lib if lib is not None else load_side("linear")
 
 
 def load_regions():
-    """libpww_hip_regions.so (region masks and the per-pixel blend of the noise predictions), loaded once, on the first call that carries
-    region prompts. A missing kernel is an error: a file that is missing, stale or broken raises with the rebuild hint."""
-    global _regions
-    if _regions is not None:
-        return _regions
-    hint = "(rebuild: python paint-with-words-sd_amd/build.py)"
-    try:
-        lib = ctypes.CDLL(REGIONS_LIB_PATH)
-        lib.pww_regions_version.restype = ctypes.c_int
-        version = lib.pww_regions_version()
-    except (OSError, AttributeError) as e:
-        raise PwwHipError("libpww_hip_regions.so at %s cannot be loaded: %s %s" % (REGIONS_LIB_PATH, e, hint))
-    if version // 100 != 1 or version < REGIONS_MIN_VERSION:
-        raise PwwHipError("libpww_hip_regions ABI version %d is not 1.x >= %d %s" % (version, REGIONS_MIN_VERSION, hint))
-    missing = [n for n in REGIONS_EXPORTS if not hasattr(lib, n)]
-    if missing:
-        raise PwwHipError("libpww_hip_regions.so at %s lacks %s %s" % (REGIONS_LIB_PATH, missing, hint))
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    lib.pww_regions_last_error.restype = ctypes.c_char_p
-    lib.pww_last_error = lib.pww_regions_last_error        # (`check(rc, what, lib)` asks the library it is given)
-    lib.pww_regions_masks.argtypes = [vp, i32, i32, vp, i32, f32, vp, vp]
-    lib.pww_regions_masks.restype = ctypes.c_int
-    lib.pww_regions_combine.argtypes = [vp, vp, vp, vp, f32, vp, i32, i32, i32, i64, i32, vp]
-    lib.pww_regions_combine.restype = ctypes.c_int
-    _regions = lib
-    return _regions
+    lib = _side.get("regions")
+    return lib if lib is not None else load_side("regions")
 
 
 class experiments:

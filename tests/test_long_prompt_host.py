@@ -173,7 +173,7 @@ def test_long_library_is_built_and_exports_what_its_header_declares(long_lib_pat
 
 def test_missing_long_library_raises(monkeypatch, tmp_path):
     from pww_hip import _lib
-    monkeypatch.setattr(_lib, "_long", None)
+    monkeypatch.setitem(_lib._side, "long", None)
     monkeypatch.setattr(_lib, "LONG_LIB_PATH", str(tmp_path / "libpww_hip_long.so"))
     with pytest.raises(_lib.PwwHipError, match="libpww_hip_long.so not found"):
         _lib.load_long()

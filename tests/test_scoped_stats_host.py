@@ -219,7 +219,7 @@ def test_missing_library_falls_back_and_a_stale_one_raises(monkeypatch, tmp_path
     assert route() is False
     monkeypatch.setattr(A, "SCOPED_STATS", True)
     # a missing file: the route is simply not taken
-    monkeypatch.setattr(_lib, "_scope", None)
+    monkeypatch.setitem(_lib._side, "scope", None)
     monkeypatch.setattr(_lib, "SCOPE_LIB_PATH", str(tmp_path / "libpww_hip_scope.so"))
     assert _lib.load_scope() is None and ops.scoped_available() is False and route() is False
     with pytest.raises(_lib.PwwHipError, match="libpww_hip_scope.so not found"):
