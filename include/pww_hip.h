@@ -427,7 +427,8 @@ int pww_mask_build_f32_levels(const float *masks, int32_t H, int32_t W, int32_t 
  * CROSS_ATTENTION_WEIGHT_ORIG [H][W][T] -> [n_tokens][T]: the reference's fallback when a layer's token count has no
  * pre-computed map (paint_with_words.py:96-101; image sizes that are not multiples of 64): bilinear
  * (align_corners=True) to (oh, ow) = floor(H / r), floor(W / r) with r = sqrt(H*W / n_tokens) -- computed by the
- * caller in double precision, as torch does -- then 1-D nearest over the flattened oh*ow pixels.
+ * caller in double precision, as torch does -- then 1-D nearest over the flattened oh*ow pixels. The resize only shrinks:
+ * oh > H, ow > W or n_tokens > H*W is PWW_EINVAL.
  */
 int pww_resize_tokens(const float *orig, int32_t H, int32_t W, int32_t T, int32_t oh, int32_t ow,
                       int32_t n_tokens, float *out, void *stream);

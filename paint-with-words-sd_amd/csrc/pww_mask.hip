@@ -192,7 +192,8 @@ __global__ void __launch_bounds__(256) resize_tokens_kernel(const float *orig, i
 
 int resize_tokens(const float *orig, int H, int W, int T, int oh, int ow, int n_tokens, float *out, hipStream_t stream) {
     if (!orig || !out) { set_error("resize_tokens: null argument"); return PWW_EINVAL; }
-    if (H <= 0 || W <= 0 || T <= 0 || oh <= 0 || ow <= 0 || n_tokens <= 0 || oh > H || ow > W) {
+    // (n_tokens > H*W, more tokens than pixels, is refused by itself: oh > H sees it only once floor(H sqrt(n / (H*W))) reaches H + 1)
+    if (H <= 0 || W <= 0 || T <= 0 || oh <= 0 || ow <= 0 || n_tokens <= 0 || oh > H || ow > W || (long)n_tokens > (long)H * W) {
         set_error("resize_tokens: bad size H=%d W=%d T=%d oh=%d ow=%d n=%d", H, W, T, oh, ow, n_tokens);
         return PWW_EINVAL;
     }

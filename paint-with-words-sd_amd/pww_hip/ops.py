@@ -713,6 +713,17 @@ def round_half_up_div(a, ratio):
     return (2 * a + ratio) // (2 * ratio)
 
 
+def _level_rows(H, W, ratios):
+    """{ratio: Hr * Wr}. A level without pixels is refused here: its empty output tensor has a null data pointer, which the C entry
+    points take for "skip this level", so the library's own refusal would never be reached."""
+    rows = {}
+    for r in ratios:
+        rows[r] = round_half_up_div(H, r) * round_half_up_div(W, r) if r > 0 else 0
+        if rows[r] <= 0:
+            raise PwwHipError("mask_build: image %dx%d too small for ratio %d" % (H, W, r))
+    return rows
+
+
 def mask_build(rgb, regions, cols, ratios=(8, 16, 32, 64)):
     """RGB color map (uint8 [H, W, 3] device tensor) -> {ratio: fp32 [Hr*Wr, T]} token weight maps.
     regions: [(r, g, b, strength)]; cols: per prompt position, the region ordinals added to it."""
@@ -723,10 +734,10 @@ def mask_build(rgb, regions, cols, ratios=(8, 16, 32, 64)):
     H, W = rgb.shape[:2]
     T = len(cols)
     dev = rgb.device
+    rows = _level_rows(H, W, ratios)
     regs = _regions_tensor(regions, dev)
     col_ptr, col_reg = _csr(cols, dev)
-    outs = {r: torch.empty((round_half_up_div(H, r) * round_half_up_div(W, r), T), dtype=torch.float32, device=dev)
-            for r in ratios}
+    outs = {r: torch.empty((rows[r], T), dtype=torch.float32, device=dev) for r in ratios}
     lib = _lib.load()
     with torch.cuda.device(dev):
         if tuple(ratios) == (8, 16, 32, 64):
@@ -748,12 +759,13 @@ def mask_build_f32(masks, cols, ratios=(8, 16, 32, 64)):
     R, H, W = masks.shape
     T = len(cols)
     dev = masks.device
+    rows = _level_rows(H, W, ratios)
     col_ptr, col_reg = _csr(cols, dev)
     outs = {}
     lib = _lib.load()
     with torch.cuda.device(dev):
         for r in ratios:
-            outs[r] = torch.empty((round_half_up_div(H, r) * round_half_up_div(W, r), T), dtype=torch.float32, device=dev)
+            outs[r] = torch.empty((rows[r], T), dtype=torch.float32, device=dev)
         rest = list(ratios)
         if all(r in outs for r in (8, 16, 32, 64)):       # the four maps of a request: ONE launch
             rc = lib.pww_mask_build_f32_levels(_ptr(masks), H, W, R, _ptr(col_ptr), _ptr(col_reg), T, _ptr(outs[8]), _ptr(outs[16]),

@@ -53,3 +53,14 @@ def rel_l2(a, b):
     a = a.detach().double().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, np.float64)
     b = b.detach().double().cpu().numpy() if torch.is_tensor(b) else np.asarray(b, np.float64)
     return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+
+
+def _blur_exact(mask, sigma, ksize=39):
+    """The same Gaussian blur in float64 (fp32 kernel weights as torchvision builds them, reflect padding): what an
+    infinitely precise conv2d would return."""
+    from pww_hip.ops import gaussian_kernel1d
+    k = gaussian_kernel1d(float(sigma), ksize).double().numpy()
+    p = ksize // 2
+    padded = np.pad(np.asarray(mask, np.float64), p, mode="reflect")
+    rows = sum(k[j] * padded[:, j:j + mask.shape[1]] for j in range(ksize))
+    return sum(k[j] * rows[j:j + mask.shape[0]] for j in range(ksize))

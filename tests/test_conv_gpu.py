@@ -131,6 +131,80 @@ def test_small_and_ragged_widths(Cin, H, W, stride, up):
     _check(y, _reference(x, w, b, stride, up), torch.bfloat16)
 
 
+# (Cin, splitk): the slabs per split, n = s_end - s_begin with s = ks * nslab / splitk. Cin 64 has 9 K-slabs, one per tap; Cin 128 has 18, two
+# per tap, so that an odd s_begin starts in the middle of a tap (ci0 = 64).
+SHORT_SPLITS = [(64, 3), (64, 4), (64, 5), (64, 9),         # n = 3;  2 or 3;  1 or 2;  1
+                (128, 5), (128, 7), (128, 9), (128, 18)]    # n = 3 or 4;  2 or 3;  2;  1
+SHORT_GEOMETRIES = [(3, 5, 7, 1, 0), (2, 9, 11, 2, 0), (2, 3, 5, 1, 1)]     # (rows, Hin, Win, stride, upsample): M = 105, 60, 120 -- a lone partial tile
+_SHORT_CASES = {}
+
+
+def _short_case(Cin, geometry, dtype):
+    """Inputs, residual and the two fp32 references (plain, with bias) of one short-split case, computed once and left unchanged."""
+    key = (Cin, geometry, dtype)
+    if key not in _SHORT_CASES:
+        rows, Hin, Win, stride, up = geometry
+        x, w, b = _inputs(rows, Cin, 128, Hin, Win, dtype, seed=6)
+        plain_ref, bias_ref = _reference(x, w, None, stride, up), _reference(x, w, b, stride, up)
+        r = torch.randn(plain_ref[0].shape, device=DEV, generator=torch.Generator(device=DEV).manual_seed(7)).to(dtype).contiguous(memory_format=CL)
+        _SHORT_CASES[key] = (x, w, b, r, plain_ref, bias_ref)
+    return _SHORT_CASES[key]
+
+
+def _ulp_ratio(y, ref_scale, dtype):
+    """max |y - ref| in units of the bar's one-step term ULP (s + 1e-2 max s): _check passes up to 2."""
+    ref, scale = ref_scale
+    return ((y.float() - ref).abs() / (ULP[dtype] * (scale + 1e-2 * scale.max()))).max().item()
+
+
+def test_short_split_counts():
+    """The splits above really give the slab counts they are there for, by the kernel's own s_begin / s_end arithmetic."""
+    want = {(64, 3): ({3}, False), (64, 4): ({2, 3}, False), (64, 5): ({1, 2}, False), (64, 9): ({1}, False),
+            (128, 5): ({3, 4}, True), (128, 7): ({2, 3}, True), (128, 9): ({2}, False), (128, 18): ({1}, True)}
+    for Cin, ns in SHORT_SPLITS:
+        nslab, per_tap = 9 * Cin // 64, Cin // 64
+        begins = [ks * nslab // ns for ks in range(ns + 1)]
+        counts = {b - a for a, b in zip(begins, begins[1:])}
+        mid_tap = any(s % per_tap for s in begins[:-1])
+        assert (counts, mid_tap) == want[(Cin, ns)], (Cin, ns, counts, mid_tap)
+        assert max(counts) <= 4 and min(counts) < 4
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("tile_n", [64, 128])
+@pytest.mark.parametrize("geometry", SHORT_GEOMETRIES, ids=lambda g: "%dx%dx%d-s%d-u%d" % g)
+@pytest.mark.parametrize("Cin,splitk", SHORT_SPLITS)
+def test_short_splits(Cin, splitk, geometry, tile_n, dtype):
+    """Splits of 1, 2 and 3 K-slabs: the K loop's steady part needs 4, so these run in the drain alone -- its conditional requests and moves,
+    with a split that starts in the middle of a tap at Cin 128. The planner never picks such a split (at least 8 slabs each), but `splitk` is a
+    public field. Plain, with bias, with bias + residual: the 2-ULP bar, the exact-epilogue identities, three bitwise equal calls.
+    (A drain that moved register set t % PF instead of (t + 1) % PF would compute slab 0 twice in every n >= 2 split; a ci0 that started at 0
+    would read the wrong 64 channels in the Cin 128 splits that begin at an odd slab. Both land far outside the bar.)"""
+    ops = _ops()
+    rows, Hin, Win, stride, up = geometry
+    x, w, b, r, plain_ref, bias_ref = _short_case(Cin, geometry, dtype)
+    kw = dict(stride=stride, upsample=bool(up), tile_n=tile_n, splitk=splitk)
+    plain = ops.conv3x3(x, w, **kw)
+    with_bias = ops.conv3x3(x, w, b, **kw)
+    fused = [ops.conv3x3(x, w, b, residual=r, **kw) for _ in range(3)]
+    print("short split Cin %d splitk %d %s tile_n %d %s: |err| / (ULP (s + 1e-2 max s)) plain %.3f, bias %.3f (bar 2)"
+          % (Cin, splitk, geometry, tile_n, dtype, _ulp_ratio(plain, plain_ref, dtype), _ulp_ratio(with_bias, bias_ref, dtype)))
+    _check(plain, plain_ref, dtype)
+    _check(with_bias, bias_ref, dtype)
+    assert torch.equal(with_bias, (plain.float() + b.float()[None, :, None, None]).to(dtype))
+    assert torch.equal(fused[0], ops.bias_residual(r, plain, b))
+    assert torch.equal(fused[0], fused[1]) and torch.equal(fused[0], fused[2])
+    assert torch.equal(plain, ops.conv3x3(x, w, **kw)) and torch.equal(with_bias, ops.conv3x3(x, w, b, **kw))
+
+
+def test_more_splits_than_slabs_is_refused():
+    ops = _ops()
+    x, w, _ = _inputs(3, 64, 128, 5, 7, torch.bfloat16, seed=6)
+    with pytest.raises(ops.PwwHipError, match="exceeds the 9 K-slabs"):
+        ops.conv3x3(x, w, splitk=10)
+    assert ops.conv3x3(x, w, splitk=9).shape == (3, 128, 5, 7)
+
+
 def test_declines():
     ops = _ops()
     x, w, _ = _inputs(2, 64, 64, 8, 8, torch.bfloat16)
