@@ -266,7 +266,9 @@ int32_t pww_qk_parts_count(const pww_attn_desc_t *desc);
  *   workspace caller-owned scratch, at least pww_group_norm_workspace_bytes(desc) bytes, 16-byte aligned, contents need not be
  *             initialised (fp64 partial sums handed from the first launch to the second).
  * One launch when a group fits one workgroup's registers (the small feature maps), else two (moments, apply) on `stream`; no atomics,
- * results bitwise repeatable. Requirements: C % G == 0, C % 8 == 0, HW % 8 == 0, G <= 32, C <= 4096 for NHWC; PWW_ENOTSUP otherwise.
+ * results bitwise repeatable. Statistics: sums of the T-rounded values and squares, fp32 within a thread, fp64 from there on; PWW_DTYPE_F16
+ * sums around a per-thread pivot, so a mean of hundreds of spreads costs no accuracy (bfloat16 squares fit fp32 sums exactly anyway).
+ * Requirements: C % G == 0, C % 8 == 0, HW % 8 == 0, G <= 32, C <= 4096 for NHWC; PWW_ENOTSUP otherwise.
  */
 #define PWW_LAYOUT_NCHW 0
 #define PWW_LAYOUT_NHWC 1

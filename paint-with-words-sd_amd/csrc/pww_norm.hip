@@ -17,8 +17,15 @@
 //     state that must be zero.
 // Rounding points are those of the stock sequence on T tensors (so the fused op can replace it under a parity test): x + t is rounded to T
 // before it is normalised, the normalised value is rounded to T before the activation, the activation's result is rounded to T. Statistics
-// are BIASED variances of the T-rounded inputs: fp32 per thread over <= 96 values, fp64 from there on (ATen: Welford in fp32),
-// rstd = 1 / sqrt(var + eps).
+// are BIASED variances of the T-rounded inputs, rstd = 1 / sqrt(var + eps): a thread sums values and squares in fp32 (the single-launch
+// forms over its <= 96 register-held values, gn_moments_nchw over 64 at a time, gn_moments_nhwc per channel over its pixels of the slab),
+// fp64 from there on (ATen: Welford in fp32). bfloat16: a square has 16 significant bits, so fp32 sums of that few same-magnitude terms
+// are exact whatever the mean. float16: a square has 22, the fp32 sums round, and under a mean of 600 spreads (300 +- 0.5) the plain
+// sums put rstd off by 6 - 8 % in gn_group_* and gn_moments_nchw (measured on MI355X: outputs 58 - 86 rounding steps from the fp64
+// reference; gn_moments_nhwc, which sums per channel over ~10 pixels, stayed within one) -- so the f16 instantiations sum d = h - c and
+// d * d around a pivot c (a value near the mean that the thread loads anyway: its first one; gn_moments_nhwc: its chunk's first
+// channel at its first pixel of the slab, handed to the fold through LDS) and add the pivot back where fp32 becomes fp64: S += s' + n c,
+// Q += q' + 2 c s' + n c c. With it all four stay within one step. The bf16 instantiations keep the plain sums (GnPivot<T>).
 // Both memory formats of a [B, C, H, W] tensor: NCHW (a group is one contiguous run of cg * HW elements) and NHWC = torch.channels_last (a
 // pixel's C channels are contiguous: what MIOpen's bf16 convolutions want).
 #include "pww_common.h"
@@ -62,6 +69,14 @@ struct GnCold {
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 template <typename T> __device__ __forceinline__ float round_to(float v) { return (float)(T)v; }
+
+// float16 statistics are summed around a pivot (header); sums (s, q) of n values h - c -> the sums of the values themselves, in fp64
+template <typename T> struct GnPivot { static constexpr bool on = false; };
+template <> struct GnPivot<f16> { static constexpr bool on = true; };
+__device__ __forceinline__ void unpivot(double &S, double &Q, double s, double q, double c, double n) {
+    S += s + n * c;
+    Q += q + 2.0 * c * s + n * c * c;
+}
 
 template <typename T, int ACT> __device__ __forceinline__ float finish(float h, float a, float b) {
     float y = round_to<T>(fmaf(a, h, b));
@@ -108,6 +123,7 @@ __global__ void __launch_bounds__(NT) gn_moments_nhwc(GN_KARGS) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) s[j] = q[j] = t[j] = pb[j] = 0.f;
         const T *x = reinterpret_cast<const T *>(p.x) + (long)b * p.HW * p.C + ch * 8;
+        float c = 0.f;                                            // f16: the thread's first value (its chunk's first channel)
         if (p.pre) {
             const V8 pv = *reinterpret_cast<const V8 *>(reinterpret_cast<const T *>(p.pre) + ch * 8);
 #pragma unroll
@@ -129,6 +145,13 @@ __global__ void __launch_bounds__(NT) gn_moments_nhwc(GN_KARGS) {
                 const int pu = px + u * PL;
                 r[u] = *reinterpret_cast<const V8 *>(x + (long)(pu < p1 ? pu : px) * p.C);
             }
+            if constexpr (GnPivot<T>::on) {
+                if (px == p0 + pl) {              // (taken from the first trip's data: no load of its own in front of the loop)
+                    c = (float)r[0][0];
+                    if (p.pre) c = round_to<T>(c + pb[0]);
+                    if (p.add) c = round_to<T>(c + t[0]);
+                }
+            }
 #pragma unroll
             for (int u = 0; u < GN_UN; ++u) {
                 const bool ok = px + u * PL < p1;
@@ -137,6 +160,7 @@ __global__ void __launch_bounds__(NT) gn_moments_nhwc(GN_KARGS) {
                     float h = (float)r[u][j];
                     if (p.pre) h = round_to<T>(h + pb[j]);
                     if (p.add) h = round_to<T>(h + t[j]);
+                    if constexpr (GnPivot<T>::on) h -= c;
                     h = ok ? h : 0.f;
                     s[j] += h;
                     q[j] = fmaf(h, h, q[j]);
@@ -145,6 +169,7 @@ __global__ void __launch_bounds__(NT) gn_moments_nhwc(GN_KARGS) {
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) { ls[pl * p.C + ch * 8 + j] = s[j]; lq[pl * p.C + ch * 8 + j] = q[j]; }
+        if constexpr (GnPivot<T>::on) reinterpret_cast<float *>(lk + (NT / p.G) * p.G * 2)[tid] = c;      // [PL][CH] pivots behind lk
     }
     __syncthreads();
     // (group, lane k of K) sums every K-th of the group's PL * cg entries; thread g < G then adds the K lanes in order
@@ -154,7 +179,14 @@ __global__ void __launch_bounds__(NT) gn_moments_nhwc(GN_KARGS) {
         const int n = PL * p.cg;
         for (int e = k; e < n; e += K) {
             const int r = e / p.cg, c = g * p.cg + (e - r * p.cg);
-            S += (double)ls[r * p.C + c]; Q += (double)lq[r * p.C + c];
+            if constexpr (GnPivot<T>::on) {       // row r of the table holds the pixels p0 + r, p0 + r + PL, ... < p1
+                const float *lc = reinterpret_cast<const float *>(lk + K * p.G * 2);
+                const int p0 = slab * p.slab_px, p1 = min(p0 + p.slab_px, p.HW);
+                const int cnt = p0 + r < p1 ? (p1 - p0 - r + PL - 1) / PL : 0;
+                unpivot(S, Q, (double)ls[r * p.C + c], (double)lq[r * p.C + c], (double)lc[r * CH + (c >> 3)], (double)cnt);
+            } else {
+                S += (double)ls[r * p.C + c]; Q += (double)lq[r * p.C + c];
+            }
         }
         lk[(k * p.G + g) * 2] = S; lk[(k * p.G + g) * 2 + 1] = Q;
     }
@@ -269,6 +301,7 @@ __global__ void __launch_bounds__(GN_NT) gn_group_nhwc(GN_KARGS) {
     const int ppp = p.cg >> 2, PLs = GN_NT / ppp;
     const int pl = tid / ppp, sub = tid - pl * ppp;
     const bool active = pl < PLs;
+    const int pc = pl < p.HW ? pl : 0;            // the pixel a masked piece loads instead: one of the image (HW < PLs: pl itself is none)
     const int c0 = g * p.cg + sub * 4;
     const T *x = reinterpret_cast<const T *>(p.x) + (long)b * p.HW * p.C + c0;
     T *y = reinterpret_cast<T *>(p.y) + (long)b * p.HW * p.C + c0;
@@ -279,7 +312,7 @@ __global__ void __launch_bounds__(GN_NT) gn_group_nhwc(GN_KARGS) {
 #pragma unroll
         for (int j = 0; j < GN_GROUP_PIECES; ++j) {
             const int px = pl + j * PLs;
-            raw[j] = *reinterpret_cast<const TV *>(x + (long)(px < p.HW ? px : pl) * p.C);
+            raw[j] = *reinterpret_cast<const TV *>(x + (long)(px < p.HW ? px : pc) * p.C);
         }
         if (p.gamma) gv = *reinterpret_cast<const TV *>(reinterpret_cast<const T *>(p.gamma) + c0);
         if (p.beta) bv = *reinterpret_cast<const TV *>(reinterpret_cast<const T *>(p.beta) + c0);
@@ -287,7 +320,8 @@ __global__ void __launch_bounds__(GN_NT) gn_group_nhwc(GN_KARGS) {
         if (p.pre) pv = *reinterpret_cast<const TV *>(reinterpret_cast<const T *>(p.pre) + c0);
     }
     float v[GN_GROUP_PIECES][4];
-    float s = 0.f, q = 0.f;
+    float s = 0.f, q = 0.f, c = 0.f;
+    int cnt = 0;                                  // f16: the thread's values, summed around its first one
     if (active) {
 #pragma unroll
         for (int j = 0; j < GN_GROUP_PIECES; ++j) {
@@ -299,12 +333,18 @@ __global__ void __launch_bounds__(GN_NT) gn_group_nhwc(GN_KARGS) {
                 if (p.add) h = round_to<T>(h + (float)tv[e]);
                 h = ok ? h : 0.f;
                 v[j][e] = h;
+                if constexpr (GnPivot<T>::on) {
+                    if (j == 0 && e == 0) c = h;
+                    h = ok ? h - c : 0.f;
+                }
                 s += h;
                 q = fmaf(h, h, q);
             }
+            if constexpr (GnPivot<T>::on) cnt += ok ? 4 : 0;
         }
     }
     double S = (double)s, Q = (double)q;
+    if constexpr (GnPivot<T>::on) { S = 0.0; Q = 0.0; unpivot(S, Q, (double)s, (double)q, (double)c, (double)cnt); }
     wg_sum(S, Q, red, tid);
     float mean, rstd;
     mean_rstd(S, Q, (double)p.cg * (double)p.HW, p.eps, mean, rstd);      // (every thread: no second barrier)
@@ -353,6 +393,8 @@ __global__ void __launch_bounds__(GN_NT) gn_moments_nchw(GN_KARGS) {
             t[u] = add ? (float)add[(ku * 8) / p.HW] : 0.f;
             pb[u] = pre ? (float)pre[(ku * 8) / p.HW] : 0.f;
         }
+        float c = 0.f;                                            // f16: the trip's values, summed around its first one (k < hi: valid)
+        int cnt = 0;
 #pragma unroll
         for (int u = 0; u < GN_UN; ++u) {
             const bool ok = k + (long)u * GN_NT < hi;
@@ -361,12 +403,20 @@ __global__ void __launch_bounds__(GN_NT) gn_moments_nchw(GN_KARGS) {
                 float h = (float)r[u][j];
                 if (pre) h = round_to<T>(h + pb[u]);
                 if (add) h = round_to<T>(h + t[u]);
+                if constexpr (GnPivot<T>::on) {
+                    if (u == 0 && j == 0) c = h;
+                    h -= c;
+                }
                 h = ok ? h : 0.f;
                 s += h;
                 q = fmaf(h, h, q);
             }
+            if constexpr (GnPivot<T>::on) cnt += ok ? 8 : 0;
         }
-        S += (double)s; Q += (double)q; s = q = 0.f;              // fp32 only over 64 elements at a time
+        // fp32 only over 64 elements at a time
+        if constexpr (GnPivot<T>::on) unpivot(S, Q, (double)s, (double)q, (double)c, (double)cnt);
+        else { S += (double)s; Q += (double)q; }
+        s = q = 0.f;
     }
     wg_sum(S, Q, red, tid);
     if (tid == 0) {
@@ -465,7 +515,8 @@ __global__ void __launch_bounds__(GN_NT) gn_group_nchw(GN_KARGS) {
         pp[j] = p.pre ? (float)reinterpret_cast<const T *>(p.pre)[c] : 0.f;
     }
     float v[MAXP][8];
-    float s = 0.f, q = 0.f;
+    float s = 0.f, q = 0.f, c = 0.f;
+    int cnt = 0;                                          // f16: the thread's values, summed around its first one
 #pragma unroll
     for (int j = 0; j < MAXP; ++j) {
         const int row = rl + (j / kper) * RP, k = k0 + (j % kper) * TPR;
@@ -477,11 +528,17 @@ __global__ void __launch_bounds__(GN_NT) gn_group_nchw(GN_KARGS) {
             if (p.add) h = round_to<T>(h + tt[j]);
             h = ok ? h : 0.f;
             v[j][e] = h;
+            if constexpr (GnPivot<T>::on) {
+                if (j == 0 && e == 0) c = h;
+                h = ok ? h - c : 0.f;
+            }
             s += h;
             q = fmaf(h, h, q);
         }
+        if constexpr (GnPivot<T>::on) cnt += ok ? 8 : 0;
     }
     double S = (double)s, Q = (double)q;
+    if constexpr (GnPivot<T>::on) { S = 0.0; Q = 0.0; unpivot(S, Q, (double)s, (double)q, (double)c, (double)cnt); }
     wg_sum(S, Q, red, tid);
     float mean, rstd;
     mean_rstd(S, Q, (double)p.cg * (double)p.HW, p.eps, mean, rstd);
@@ -532,7 +589,7 @@ bool gn_plan(const pww_gn_desc_t *d, GnPlan &pl) {
         pl.apply_px = apx;
         pl.partial_bytes = (size_t)d->B * pl.nslab * d->G * 2 * sizeof(double);
         const size_t lk = (size_t)(pl.nt / d->G) * d->G * 2 * sizeof(double);
-        pl.lds_m = (size_t)2 * PL * d->C * sizeof(float) + lk;
+        pl.lds_m = (size_t)2 * PL * d->C * sizeof(float) + lk + (d->dtype == PWW_DTYPE_F16 ? (size_t)pl.nt * sizeof(float) : 0);      // (+ the pivots)
         pl.lds_a = lk + (size_t)d->G * 2 * sizeof(float);
     } else {
         const long nchunk = (long)cg * d->HW / 8;

@@ -979,6 +979,8 @@ def add_layer_norm(x, weight, bias, eps, a=None, post_bias=None):
     if rx is None:
         x = x.contiguous()
         rx = _rows(x, "add_layer_norm")
+    if rx is None:                                  # (contiguous rows that still do not qualify: C no multiple of 8)
+        raise PwwHipError("add_layer_norm: the last dim must be a multiple of 8 (got %d)" % x.shape[-1])
     rows, C, xs = rx
     ra = None
     if a is not None:
@@ -1013,6 +1015,8 @@ def geglu(h):
     if r is None:
         h = h.contiguous()
         r = _rows(h, "geglu")
+    if r is None:
+        raise PwwHipError("geglu: the last dim must be 2 * D with D a multiple of 8 (got %d)" % h.shape[-1])
     rows, C2, hs = r
     if C2 % 16 != 0:
         raise PwwHipError("geglu: the last dim must be 2 * D with D a multiple of 8 (got %d)" % C2)
