@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Six libraries come out of the same sources:
+Seven libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
                               measured and not made a default (include/pww_hip.h, section "experiments"). Built by the tests / tools that
@@ -12,11 +12,12 @@ Six libraries come out of the same sources:
                               headers (its host plumbing is pww_side_host.h), its own entry points pww_<name>_* declared in
                               include/pww_hip_<name>.h and the only visible symbols, loaded by the package on the first call that needs
                               them (pww_hip/_lib.py, `load_side(name)`). `build_side(name)`, or the aliases `build_long()` ...
-                              `build_regions()`; __graft_entry__.build() compiles all of them beside the product library.
+                              `build_lora()`; __graft_entry__.build() compiles all of them beside the product library.
                                 long      the cross-attention launches of prompts longer than 77 tokens (128 < M <= 256 keys)
                                 scope     cross-attention whose bias coefficient is a per-head or per-row score statistic (M <= 128 keys)
                                 linear    linear layers with a bias / residual / GEGLU epilogue
                                 regions   region prompts: the region masks at latent resolution and the per-pixel blend of the noise predictions
+                                lora      unmerged LoRA adapters chosen per batch row: the low-rank update behind the attention projections
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -46,11 +47,14 @@ SIDE_LIBS = {
     "scope": ("pww_scope.hip", _ATTN_HEADERS, "cross-attention with per-head / per-row score statistics"),
     "linear": ("pww_linear.hip", [], "linear layers with a bias / residual / GEGLU epilogue"),
     "regions": ("pww_regions.hip", [], "region masks and the per-pixel blend of the noise predictions"),
+    "lora": ("pww_lora.hip", [], "the per-row low-rank update of unmerged LoRA adapters"),
 }
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
 HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_attn_kernel.h", "pww_cross_tile.h", "pww_cross_kernel.h", os.path.join(REPO, "include", "pww_hip.h")]
-LIB_LONG, LIB_SCOPE, LIB_LINEAR, LIB_REGIONS = (os.path.join(HERE, "pww_hip", "libpww_hip_%s.so" % n) for n in SIDE_LIBS)
-LONG_UNITS, SCOPE_UNITS, LINEAR_UNITS, REGIONS_UNITS = ([(v[0], SIDE_FLAGS, "")] for v in SIDE_LIBS.values())     # (as in UNITS)
+SIDE_PATHS = {n: os.path.join(HERE, "pww_hip", "libpww_hip_%s.so" % n) for n in SIDE_LIBS}
+SIDE_UNITS = {n: [(v[0], SIDE_FLAGS, "")] for n, v in SIDE_LIBS.items()}     # (as in UNITS)
+LIB_LONG, LIB_SCOPE, LIB_LINEAR, LIB_REGIONS, LIB_LORA = (SIDE_PATHS[n] for n in ("long", "scope", "linear", "regions", "lora"))
+LONG_UNITS, SCOPE_UNITS, LINEAR_UNITS, REGIONS_UNITS, LORA_UNITS = (SIDE_UNITS[n] for n in ("long", "scope", "linear", "regions", "lora"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
 # into SGPRs by the dispatcher instead of fetched by the wave's first s_load (gfx950 supports kernarg preload; the compiler keeps a compatibility
@@ -120,17 +124,18 @@ def build_experiments(force=False, verbose=False):
 def build_side(name, force=False, verbose=False):
     """libpww_hip_<name>.so, one of SIDE_LIBS (include/pww_hip_<name>.h)."""
     unit, headers, _ = SIDE_LIBS[name]
-    lib = os.path.join(HERE, "pww_hip", "libpww_hip_%s.so" % name)
+    lib = SIDE_PATHS[name]
     deps = [os.path.join(CSRC, f) for f in [unit, "pww_common.h", "pww_side_host.h"] + headers] + [os.path.join(REPO, "include", h) for h in ("pww_hip.h", "pww_hip_%s.h" % name)] + [__file__]
     if not force and not _newer(lib, deps):
         return lib
-    return _build(lib, [(unit, SIDE_FLAGS, "")], [], os.path.join(HERE, "build", name), verbose)
+    return _build(lib, SIDE_UNITS[name], [], os.path.join(HERE, "build", name), verbose)
 
 
 def build_long(force=False, verbose=False): return build_side("long", force, verbose)  # noqa: E704
 def build_scope(force=False, verbose=False): return build_side("scope", force, verbose)  # noqa: E704
 def build_linear(force=False, verbose=False): return build_side("linear", force, verbose)  # noqa: E704
 def build_regions(force=False, verbose=False): return build_side("regions", force, verbose)  # noqa: E704
+def build_lora(force=False, verbose=False): return build_side("lora", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):

@@ -1,4 +1,4 @@
-// Host plumbing of a side library (libpww_hip_long.so, _scope, _linear, _regions): the few host helpers pww_common.h declares, defined once
+// Host plumbing of a side library (libpww_hip_long.so, _scope, _linear, _regions, _lora): the few host helpers pww_common.h declares, defined once
 // per library. A side library's one translation unit includes this exactly once, after
 //
 //   #define PWW_SIDE_LIB "libpww_hip_<x>"

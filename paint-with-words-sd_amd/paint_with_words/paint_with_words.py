@@ -22,7 +22,7 @@ from PIL import Image
 import pww_hip
 from pww_hip.attention import inj_forward  # noqa: F401  (same import path as the reference's symbol)
 from pww_hip.conditioning import check_prompt_chunks, prompt_chunk_count, check_negative_context
-from pww_hip.conditioning import check_region_prompts, region_entries, encode_region_prompts
+from pww_hip.conditioning import check_region_prompts, check_loras, region_entries, encode_region_prompts
 from pww_hip.conditioning import (always_round, _extract_seed_and_sigma_from_context, _encode_text_color_inputs,  # noqa: F401
                                   _get_binary_mask, gaussian_blur_mask)
 from pww_hip.sampler import PwWSampler, initial_latents
@@ -183,7 +183,7 @@ def _txt2img_or_img2img(sizes, init_images, strength):
 def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
               unconditional_input_prompt, start, strength=None, map_sizes=None, on_step=None, use_region_sigma=True, shared=False,
               max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0, region_prompts=None, region_base_weight=0.0,
-              region_feather=0.0):
+              region_feather=0.0, loras=None):
     """The body behind every face of the package (reference :414-506, paint_with_words_inpaint.py:160-262): conditioning per request (once
     if `shared`: every request has the same map, context and prompt), the timesteps, the initial state, one denoise loop over all images.
     Returns the final latents [n, 4, h, w].
@@ -192,7 +192,8 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
     number the img2img tail of the schedule (:434-441). map_sizes: one (width, height) per request to resize its color map to (the inpaint
     function API, paint_with_words_inpaint.py:172). negative_color_contexts: None, or one dict (or None) per request like color_contexts --
     regions of the unconditional prompt (see paint_with_words). region_prompts: None, or one dict per request (_region_requests) -- a full
-    prompt per colour, blended per latent pixel where guidance is combined (see paint_with_words)."""
+    prompt per colour, blended per latent pixel where guidance is combined (see paint_with_words). loras: None, or what check_loras made of the
+    `lora` / `region_loras` keywords."""
     unet, text_encoder, tokenizer, scheduler = tools[1:]
     n = len(seeds)
     sampler = _sampler_for(unet, scheduler)   # also installs the attention plug
@@ -228,6 +229,9 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
 
     latents, extra_channels = start(tools, device, seeds, timesteps, seeds_info)
     more = {} if regions is None else {"regions": regions}        # (a call without region prompts is, argument for argument, the call of before)
+    if loras is not None:
+        colors = [[e[0] for e in region_entries(r)] for r in region_prompts] if region_prompts else [[]] * n
+        more["lora_rows"] = pww_hip.lora.row_plan(n, colors, loras[0], loras[1], pww_hip.lora.state_of(unet).index)
     with pww_hip.miopen_find():
         return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra_channels,
                               on_step=on_step, negative_strength=negative_strength, **more)
@@ -266,6 +270,8 @@ def paint_with_words(
     return_latents: bool = False,
     negative_color_context: Optional[Dict[Tuple[int, int, int], str]] = None,
     negative_strength: float = 1.0,
+    lora=None,
+    region_loras=None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -287,17 +293,23 @@ def paint_with_words(
     colour k (feathered by a Gaussian of `region_feather` latent pixels, at most 8) and w_k = (1 - region_base_weight) weight_k M_k,
     noise = e_u + (1 - sum w_k) g (e_prompt - e_u) + sum_k w_k s_k (e_k - e_u) -- `input_prompt` keeps the share `region_base_weight`
     in [0, 1) inside the regions and everything outside them; s_k is region k's guidance scale (the call's by default). None / {} is the
-    call without the feature. Not combined with negative_color_context."""
+    call without the feature. Not combined with negative_color_context.
+    `lora` / `region_loras` (extension): LoRA adapters loaded with pww_hip.lora.load_lora(unet, source, name) on the UNet of
+    `preloaded_utils`, applied unmerged and per row of the UNet evaluation: lora = "name" or ("name", scale) is the adapter of the prompt's
+    row, the unconditional row and every region without an adapter of its own (alone it behaves like merged weights); region_loras =
+    {(r, g, b) | "#rrggbb": "name" | ("name", scale)} gives a colour of region_prompts its own adapter."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context)
+    loras = check_loras(lora, region_loras, region_prompts, tools=preloaded_utils)
     color_map_image.size     # the reference dereferences it unconditionally (:414): None raises here too
     tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
     start, strength = _txt2img_or_img2img([color_map_image.size], None if init_image is None else [init_image], strength)
     latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps, guidance_scale,
                         weight_function, unconditional_input_prompt, start, strength, shared=True, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=[negative_color_context], negative_strength=negative_strength,
-                        region_prompts=_region_requests(region_prompts, 1), region_base_weight=region_base_weight, region_feather=region_feather)
+                        region_prompts=_region_requests(region_prompts, 1), region_base_weight=region_base_weight, region_feather=region_feather,
+                        loras=loras)
     out = _finish(tools, latents, return_latents)
     return out if return_latents else out[0]
 
@@ -323,6 +335,8 @@ def paint_with_words_batch(
     return_latents: bool = False,
     negative_color_context: Union[None, Dict, Sequence[Optional[Dict]]] = None,
     negative_strength: float = 1.0,
+    lora=None,
+    region_loras=None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -338,12 +352,14 @@ def paint_with_words_batch(
     (or the [n, 4, h, w] latents with return_latents=True). negative_color_context / negative_strength: see paint_with_words; one dict
     shared by every request or one (or None) per seed, like color_contexts. max_prompt_chunks: see paint_with_words; with per-image prompts
     every image is padded (with empty chunks) to the largest chunk count of the batch. region_prompts / region_base_weight / region_feather:
-    see paint_with_words; one dict for all requests or one per seed, every request with the same number of regions."""
+    see paint_with_words; one dict for all requests or one per seed, every request with the same number of regions. lora / region_loras: see
+    paint_with_words; `lora` serves every request, region_loras is one dict for all requests or one (or None) per seed."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     seeds = list(seeds)
     n = len(seeds)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context, n_requests=n)
+    loras = check_loras(lora, region_loras, region_prompts, n_requests=n, tools=preloaded_utils)
     if n == 0:
         return []
     ctxs, negs, maps, prompts, shared, strip = _batch_requests(n, color_contexts, negative_color_context, color_map_images, input_prompts,
@@ -357,7 +373,7 @@ def paint_with_words_batch(
     latents = _generate(tools, device, ctxs, maps, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
                         unconditional_input_prompt, start, strength, shared=shared, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=negs, negative_strength=negative_strength, region_prompts=_region_requests(region_prompts, n),
-                        region_base_weight=region_base_weight, region_feather=region_feather)
+                        region_base_weight=region_base_weight, region_feather=region_feather, loras=loras)
     for c in strip:
         _extract_seed_and_sigma_from_context(c)
     return _finish(tools, latents, return_latents)

@@ -13,7 +13,7 @@ from PIL import Image
 
 from pww_hip import ops
 from .paint_with_words import (LMSDiscreteScheduler, _tools, _generate, _finish, _broadcast, _batch_requests, check_prompt_chunks,
-                               check_negative_context, check_region_prompts, _region_requests, preprocess, _extract_seed_and_sigma_from_context)
+                               check_negative_context, check_region_prompts, check_loras, _region_requests, preprocess, _extract_seed_and_sigma_from_context)
 
 
 def _as_uint8_pixels(image, channels):
@@ -153,23 +153,27 @@ def paint_with_words_inpaint(
     return_latents: bool = False,
     negative_color_context: Optional[Dict[Tuple[int, int, int], str]] = None,
     negative_strength: float = 1.0,
+    lora=None,
+    region_loras=None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
     max_prompt_chunks: int = 1,
 ):
     """reference :137-270. negative_color_context / negative_strength / region_prompts / region_base_weight / region_feather /
-    max_prompt_chunks (extensions): see paint_with_words. The region masks are read from the color map resized to the init image: its size
+    max_prompt_chunks / lora / region_loras (extensions): see paint_with_words. The region masks are read from the color map resized to the init image: its size
     must be 8 x the latent's (a multiple of 32)."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context)
+    loras = check_loras(lora, region_loras, region_prompts, tools=preloaded_utils)
     tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
     latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps, guidance_scale,
                         weight_function, unconditional_input_prompt, partial(_inpaint_start, init_images=[init_image], mask_images=[mask_image]),
                         strength, map_sizes=[init_image.size], shared=True, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=[negative_color_context], negative_strength=negative_strength,
-                        region_prompts=_region_requests(region_prompts, 1), region_base_weight=region_base_weight, region_feather=region_feather)
+                        region_prompts=_region_requests(region_prompts, 1), region_base_weight=region_base_weight, region_feather=region_feather,
+                        loras=loras)
     out = _finish(tools, latents, return_latents)
     return out if return_latents else out[0]
 
@@ -196,6 +200,8 @@ def paint_with_words_inpaint_batch(
     return_latents: bool = False,
     negative_color_context: Union[None, Dict, Sequence[Optional[Dict]]] = None,
     negative_strength: float = 1.0,
+    lora=None,
+    region_loras=None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -204,12 +210,13 @@ def paint_with_words_inpaint_batch(
     """len(seeds) inpainting requests through one denoise loop (see paint_with_words_batch): each of the image-like
     arguments and the prompt is one shared value or a sequence with one entry per seed; all init images of a call must
     have the same size. Image i equals the single-request call on request i. negative_color_context / negative_strength /
-    region_prompts / region_base_weight / region_feather / max_prompt_chunks: see paint_with_words_batch."""
+    region_prompts / region_base_weight / region_feather / max_prompt_chunks / lora / region_loras: see paint_with_words_batch."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     seeds = list(seeds)
     n = len(seeds)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context, n_requests=n)
+    loras = check_loras(lora, region_loras, region_prompts, n_requests=n, tools=preloaded_utils)
     if n == 0:
         return []
     # (private copies are parsed when the requests differ; this function strips the caller's negative dicts only afterwards)
@@ -224,7 +231,7 @@ def paint_with_words_inpaint_batch(
                         unconditional_input_prompt, partial(_inpaint_start, init_images=inits, mask_images=masks), strength,
                         map_sizes=[im.size for im in inits], shared=shared, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=negs, negative_strength=negative_strength, region_prompts=_region_requests(region_prompts, n),
-                        region_base_weight=region_base_weight, region_feather=region_feather)
+                        region_base_weight=region_base_weight, region_feather=region_feather, loras=loras)
     for c in strip:
         _extract_seed_and_sigma_from_context(c)
     return _finish(tools, latents, return_latents)

@@ -25,7 +25,7 @@ from PIL import Image
 
 import pww_hip
 from .paint_with_words import (LMSDiscreteScheduler, _generate, _finish, _pil_from_latents, _txt2img_or_img2img, check_prompt_chunks,
-                               check_negative_context, check_region_prompts, _region_requests)
+                               check_negative_context, check_region_prompts, check_loras, _region_requests)
 from .paint_with_words_inpaint import _inpaint_start
 
 _warned = set()
@@ -55,6 +55,10 @@ class PaintWithWord_StableDiffusionPipeline:
     region_prompts = None
     region_base_weight = 0.0
     region_feather = 0.0
+    # extension: LoRA adapters (see paint_with_words), loaded with pww_hip.lora.load_lora(pipe.unet, source, name): `pipe.lora = "name"` or
+    # `("name", scale)`, `pipe.region_loras = {(r, g, b): "name"}` for the colours of `pipe.region_prompts`. Attributes for the same reason.
+    lora = None
+    region_loras = None
 
     def __init__(self, vae, text_encoder, tokenizer, unet, scheduler=None, safety_checker=None, feature_extractor=None,
                  requires_safety_checker: bool = False):
@@ -101,6 +105,8 @@ class PaintWithWord_StableDiffusionPipeline:
         check_prompt_chunks(self.max_prompt_chunks)
         check_negative_context(self.negative_color_context, self.negative_strength)
         check_region_prompts(self.region_prompts, self.region_base_weight, self.region_feather, self.negative_color_context)
+        unet = getattr(self, "unet", None)
+        return check_loras(self.lora, self.region_loras, self.region_prompts, tools=None if unet is None else (None, unet))
 
     def _check_inputs(self, prompt, height, width, negative_prompt, num_images_per_prompt, generator, latents, callback_steps):
         """The argument block both __call__s share (check_inputs of the diffusers base class, :431) -> (prompt, height, width,
@@ -123,7 +129,7 @@ class PaintWithWord_StableDiffusionPipeline:
         return prompt, height, width, negative_prompt or ""
 
     def _run(self, start, strength, prompt, color_map_image, color_context, weight_function, num_inference_steps, guidance_scale,
-             negative_prompt, seed, output_type, return_dict, callback, callback_steps):
+             negative_prompt, seed, output_type, return_dict, callback, callback_steps, loras=None):
         """One request through the generation body of the function API, returned as the diffusers pipeline returns it (:821-842). The
         reference calls `callback(i, t, latents)` every `callback_steps` steps (:815-816)."""
         on_step = None if callback is None else (lambda i, t, latents: callback(i, t, latents) if i % callback_steps == 0 else None)
@@ -132,7 +138,7 @@ class PaintWithWord_StableDiffusionPipeline:
                         weight_function, negative_prompt, start, strength, on_step=on_step, use_region_sigma=False, shared=True,
                         max_prompt_chunks=self.max_prompt_chunks, negative_color_contexts=[self.negative_color_context],
                         negative_strength=self.negative_strength, region_prompts=_region_requests(self.region_prompts, 1),
-                        region_base_weight=self.region_base_weight, region_feather=self.region_feather)
+                        region_base_weight=self.region_base_weight, region_feather=self.region_feather, loras=loras)
         images = _finish(tools, lat, decode=lambda vae, latents: _decode(vae, latents, output_type))
         return SimpleNamespace(images=images, nsfw_content_detected=False) if return_dict else (images, False)
 
@@ -160,12 +166,12 @@ class PaintWithWord_StableDiffusionPipeline:
         callback_steps: Optional[int] = 1,
     ):
         """reference :629-842 (same parameter list, order and defaults). Prompts longer than 75 tokens: `self.max_prompt_chunks`."""
-        self._check_extensions()
+        loras = self._check_extensions()
         prompt, height, width, negative_prompt = self._check_inputs(prompt, height, width, negative_prompt, num_images_per_prompt, generator,
                                                                     latents, callback_steps)
         start, strength = _txt2img_or_img2img([(width, height)], None if image is None else [image], eta)
         return self._run(start, strength, prompt, color_map_image, color_context, weight_function, num_inference_steps, guidance_scale,
-                         negative_prompt, seed, output_type, return_dict, callback, callback_steps)
+                         negative_prompt, seed, output_type, return_dict, callback, callback_steps, loras=loras)
 
 
 class PaintWithWord_StableDiffusionInpaintPipeline(PaintWithWord_StableDiffusionPipeline):
@@ -195,11 +201,11 @@ class PaintWithWord_StableDiffusionInpaintPipeline(PaintWithWord_StableDiffusion
     ):
         """reference paint_with_words_inpaint.py:340-575 (same parameter list, order and defaults). Prompts longer than 75 tokens:
         `self.max_prompt_chunks`."""
-        self._check_extensions()
+        loras = self._check_extensions()
         if image is None or mask_image is None:
             raise ValueError("`image` and `mask_image` are required for inpainting")
         prompt, height, width, negative_prompt = self._check_inputs(prompt, height, width, negative_prompt, num_images_per_prompt, generator,
                                                                     latents, callback_steps)
         start = partial(_inpaint_start, init_images=[image], mask_images=[mask_image], mask_hw=(height, width), resize_inputs=False)
         return self._run(start, eta, prompt, color_map_image, color_context, weight_function, num_inference_steps, guidance_scale,
-                         negative_prompt, seed, output_type, return_dict, callback, callback_steps)
+                         negative_prompt, seed, output_type, return_dict, callback, callback_steps, loras=loras)

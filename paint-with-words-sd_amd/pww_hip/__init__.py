@@ -4,6 +4,7 @@ and a missing library raises PwwHipError (no fallback)."""
 from ._lib import PwwHipError, load as load_library, device_arch, LIB_PATH, EXPORTS
 from . import ops
 from . import blocks
+from . import lora
 from .attention import QKProxy, ScaledW, inj_forward, install, uninstall, PwWAttnProcessor, pww_attention
 from .attnmaps import record_attention_maps, AttentionMaps
 

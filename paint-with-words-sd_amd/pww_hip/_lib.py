@@ -21,6 +21,8 @@ LONG_LIB_PATH = os.environ.get("PWW_HIP_LONG_LIB", os.path.join(_HERE, "libpww_h
 SCOPE_LIB_PATH = os.environ.get("PWW_HIP_SCOPE_LIB", os.path.join(_HERE, "libpww_hip_scope.so"))
 LINEAR_LIB_PATH = os.environ.get("PWW_HIP_LINEAR_LIB", os.path.join(_HERE, "libpww_hip_linear.so"))
 REGIONS_LIB_PATH = os.environ.get("PWW_HIP_REGIONS_LIB", os.path.join(_HERE, "libpww_hip_regions.so"))
+#   lora      unmerged LoRA adapters chosen per batch row (include/pww_hip_lora.h): ops.lora_update. Its spec is in SIDE_MORE below.
+LORA_LIB_PATH = os.environ.get("PWW_HIP_LORA_LIB", os.path.join(_HERE, "libpww_hip_lora.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 126        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -65,6 +67,12 @@ LINEAR_MIN_VERSION = 100
 REGIONS_EXPORTS = ("pww_regions_version", "pww_regions_last_error", "pww_regions_masks", "pww_regions_combine")
 REGIONS_MIN_VERSION = 100
 REGIONS_MAX, REGIONS_MAX_PLANE, REGIONS_MAX_FEATHER = 8, 9216, 8.0      # PWW_REGIONS_MAX* of the header
+
+
+# every symbol include/pww_hip_lora.h declares for libpww_hip_lora.so
+LORA_EXPORTS = ("pww_lora_version", "pww_lora_last_error", "pww_lora_fwd")
+LORA_MIN_VERSION = 100
+LORA_MAX_ADAPTERS, LORA_MAX_RANK, LORA_MAX_SEGMENTS = 8, 128, 3      # PWW_LORA_MAX_* of the header
 
 
 class AttnDesc(ctypes.Structure):
@@ -120,6 +128,13 @@ class ProbsDesc(ctypes.Structure):
     """struct pww_probs_desc (head-averaged cross-attention probabilities; size-prefixed)."""
     _fields_ = [("size", ctypes.c_uint32), ("images", ctypes.c_int32), ("accumulate", ctypes.c_int32), ("weight", ctypes.c_float),
                 ("out_stride", ctypes.c_int64 * 2)]
+
+
+class LoraDesc(ctypes.Structure):
+    """struct pww_lora_desc (per-row low-rank update; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("R", ctypes.c_int32), ("T", ctypes.c_int32), ("K", ctypes.c_int32),
+                ("N", ctypes.c_int32), ("n_seg", ctypes.c_int32), ("rank", ctypes.c_int32), ("n_adapters", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("x_row_stride", ctypes.c_int64), ("x_tok_stride", ctypes.c_int64), ("y_row_stride", ctypes.c_int64), ("y_tok_stride", ctypes.c_int64)]
 
 
 class Region(ctypes.Structure):
@@ -293,17 +308,28 @@ SIDE = {
         "pww_regions_masks": ([_vp, _i32, _i32, _vp, _i32, _f32, _vp, _vp], _int),
         "pww_regions_combine": ([_vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _i64, _i32, _vp], _int)}),
 }
+# the libraries that came after the four of SIDE: the same fields, the same loader
+SIDE_MORE = {
+    "lora": dict(path="LORA_LIB_PATH", exports=LORA_EXPORTS, min_version=LORA_MIN_VERSION, missing_ok=False, needs="LoRA adapters on the native kernel need it", sigs={
+        "pww_lora_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _P(LoraDesc), _vp], _int)}),
+}
 _side = {}      # name -> loaded handle
 
 
+def side_spec(name):
+    """The table entry of a side library (SIDE or SIDE_MORE)."""
+    return SIDE[name] if name in SIDE else SIDE_MORE[name]
+
+
 def load_side(name):
-    """libpww_hip_<name>.so of SIDE, loaded once. A missing file returns None where the table says so (scope: the caller keeps the
+    """libpww_hip_<name>.so of SIDE / SIDE_MORE, loaded once. A missing file returns None where the table says so (scope: the caller keeps the
     materialised route) and raises otherwise -- there is no second implementation to fall back to. A file that is there but stale, broken
     or short of an entry point raises. Every failure is a PwwHipError with the rebuild hint."""
     lib = _side.get(name)
     if lib is not None:
         return lib
-    spec, path, so, pre = SIDE[name], globals()[SIDE[name]["path"]], "libpww_hip_%s.so" % name, "pww_%s_" % name
+    spec = side_spec(name)
+    path, so, pre = globals()[spec["path"]], "libpww_hip_%s.so" % name, "pww_%s_" % name
     if not os.path.isfile(path):
         if spec["missing_ok"]:
             return None
@@ -347,6 +373,11 @@ def load_linear():
 def load_regions():
     lib = _side.get("regions")
     return lib if lib is not None else load_side("regions")
+
+
+def load_lora():
+    lib = _side.get("lora")
+    return lib if lib is not None else load_side("lora")
 
 
 class experiments:

@@ -51,6 +51,17 @@ FUSE_TO_OUT = False
 SCOPED_STATS = os.environ.get("PWW_SCOPED_STATS", "1") != "0"
 SCOPE_IMAGE, SCOPE_HEAD, SCOPE_ROW = 0, ops.SCOPE_HEAD, ops.SCOPE_ROW      # what a LazyStat reduces over: all of an image's scores / one head's / one query row's
 QPROJ_STAT = os.environ.get("PWW_QPROJ_STAT", "1")       # "1" where it wins (default) | "0" never | "all" wherever the kernel supports the shape
+# LoRA adapters (pww_hip/lora.py): a module that any loaded adapter touches carries a lora.LoraLayer under this attribute, and every one of
+# its projections is followed by ops.lora_update -- the low-rank update with the adapter and scale of each batch row. Such a layer declines
+# the to_q-GEMM-with-statistic route (the statistic would be formed over an un-adapted Q) and the opt-in attention + to_out launch; the
+# decision is per layer and static while an adapter is loaded. Without the attribute none of these branches is entered.
+LORA_ATTR = "_pww_lora"
+_Q, _KV, _QKV, _OUT = ("to_q",), ("to_k", "to_v"), ("to_q", "to_k", "to_v"), ("to_out.0",)
+
+
+def _lora_update(lo, y, x, names):
+    """y += s (x A^T) B^T per row for the projections `names` of the layer (one column segment each), in place."""
+    return ops.lora_update(y, x, lo.stack(names), lo.state, len(names))
 
 
 def qproj_route(C, D):
@@ -352,6 +363,9 @@ class _LazyQuery:
     def get(self):
         if self.value is None:
             self.value = self.attn.to_q(self.hidden)
+            lo = self.attn.__dict__.get(LORA_ATTR)
+            if lo is not None:
+                _lora_update(lo, self.value, self.hidden, _Q)
         return self.value
 
 
@@ -639,7 +653,13 @@ def refresh_kv_cache(context):
     ctx = context["CONTEXT_TENSOR"]
     for attn, kv in cache.values():
         w = _fused_weight(attn, ("to_k", "to_v"), kv.dtype)
-        kv.copy_(F.linear(ctx.to(w.dtype), w))
+        lo = attn.__dict__.get(LORA_ATTR)
+        if lo is None:
+            kv.copy_(F.linear(ctx.to(w.dtype), w))
+        else:       # the adapted K|V of this request's rows: the assignment was written before (sampler)
+            x = ctx.to(w.dtype)
+            x = x.expand(kv.shape[0], -1, -1) if x.shape[0] != kv.shape[0] else x
+            kv.copy_(_lora_update(lo, F.linear(x, w), x, _KV))
 
 
 def pww_attention(attn, hidden_states, context=None):
@@ -651,8 +671,14 @@ def pww_attention(attn, hidden_states, context=None):
 def _attention_and_out(attn, hidden_states, context):
     """inj_forward's :63-123: the attention and to_out[0] (to_out[1], the dropout, is the caller's)."""
     lin = attn.to_out[0]
-    out, projected = _attention(attn, hidden_states, context, lin if FUSE_TO_OUT else None)
-    return out if projected else lin(out.to(lin.weight.dtype))
+    lo = attn.__dict__.get(LORA_ATTR)
+    out, projected = _attention(attn, hidden_states, context, lin if FUSE_TO_OUT and lo is None else None)
+    if projected:
+        return out
+    if lo is None:
+        return lin(out.to(lin.weight.dtype))
+    x = out.to(lin.weight.dtype)
+    return _lora_update(lo, lin(x), x, _OUT)
 
 
 def _attention(attn, hidden_states, context, out_linear):
@@ -682,18 +708,27 @@ def _attention(attn, hidden_states, context, out_linear):
     # :60 / :392: fp16 UNet or not, fp32 text encoder :171) that is the autocast dtype, and the concatenated weights are kept
     # in it, so autocast has nothing left to cast per call.
     pdt = _compute_dtype(attn)
+    lo = attn.__dict__.get(LORA_ATTR)
+    if lo is not None and context is not None and context_tensor.shape[0] != hidden_states.shape[0]:
+        context_tensor = context_tensor.expand(hidden_states.shape[0], -1, -1)      # one row of K|V per row of the assignment
     if context is None and (w_qkv := _fused_weight(attn, ("to_q", "to_k", "to_v"), pdt)) is not None:
         qkv = F.linear(hidden_states.to(pdt), w_qkv)            # self-attention: ONE GEMM, q/k/v are strided views
+        if lo is not None:
+            _lora_update(lo, qkv, hidden_states.to(pdt), _QKV)
         query, key, value = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
     elif context is not None and (w_kv := _fused_weight(attn, ("to_k", "to_v"), pdt)) is not None:
         if is_dict:
             lazy_q = _LazyQuery(attn, hidden_states, pdt if pdt in _HALF else torch.bfloat16)      # deferred: see the symbolic-bias branch below
         else:
             query = attn.to_q(hidden_states)
+            if lo is not None:
+                _lora_update(lo, query, hidden_states, _Q)
         kv_cache = context.get(KV_CACHE) if is_dict else None
         ent = kv_cache.get(id(attn)) if kv_cache is not None else None
         if ent is None:
             kv = F.linear(context_tensor.to(pdt), w_kv)         # cross-attention: K|V in one GEMM ...
+            if lo is not None:
+                _lora_update(lo, kv, context_tensor.to(pdt), _KV)
             if kv_cache is not None:
                 kv_cache[id(attn)] = (attn, kv)                 # ... and once per request: the prompt is constant over the steps
         else:
@@ -703,6 +738,10 @@ def _attention(attn, hidden_states, context, out_linear):
         query = attn.to_q(hidden_states)
         key = attn.to_k(context_tensor)
         value = attn.to_v(context_tensor)
+        if lo is not None:
+            _lora_update(lo, query, hidden_states, _Q)
+            _lora_update(lo, key, context_tensor, ("to_k",))
+            _lora_update(lo, value, context_tensor, ("to_v",))
     if lazy_q is not None:
         cdt = key.dtype if key.dtype in _HALF else torch.bfloat16
         key, value = _half(key, cdt), _half(value, cdt)
@@ -775,7 +814,7 @@ def _attention(attn, hidden_states, context, out_linear):
         have_stats = bias.stat is not None and bias.stat._proxy._stats is not None
         # Q and the statistic's partials from ONE launch (the to_q GEMM with the score statistic in its epilogue): taken when the weight
         # function left both untouched (nobody asked for the query or the statistics as tensors) and the GEMM covers the shape
-        if (qproj_route(hidden_states.shape[-1], hidden_states.shape[-1] // attn.heads) and lazy_q is not None and not lazy_q.done and not have_stats and kind != ops.STAT_NONE and pdt in _HALF
+        if (lo is None and qproj_route(hidden_states.shape[-1], hidden_states.shape[-1] // attn.heads) and lazy_q is not None and not lazy_q.done and not have_stats and kind != ops.STAT_NONE and pdt in _HALF
                 and key.dtype == pdt and key.shape[1] <= ops.FUSED_MAX_KEYS and getattr(attn.to_q, "bias", None) is None):
             wq = _fused_weight(attn, ("to_q",), pdt)
             x = hidden_states if hidden_states.dtype == pdt else hidden_states.to(pdt)

@@ -192,6 +192,55 @@ def check_region_prompts(region_prompts, region_base_weight=0.0, region_feather=
     return counts[0] if counts else 0
 
 
+def check_loras(lora, region_loras, region_prompts=None, n_requests=None, tools=None):
+    """The `lora` / `region_loras` keywords of the entry points, checked before any model is touched.
+    lora: None, "name" or ("name", scale) -- the adapter of every row without one of its own (the conditional / base row, the unconditional
+    row, region rows without an entry). region_loras: None or {} (off), {(r, g, b) | "#rrggbb": "name" | ("name", scale)} whose colours are
+    keys of the same request's region_prompts, or -- the batch forms, `n_requests` given -- a sequence with one dict (or None) per request.
+    Names are resolved against the UNet of `tools` (the call's preloaded_utils; without one nothing can be loaded). Scales are finite numbers.
+    -> None when both are off, else ((name, scale) or None, [per request: {(r, g, b): (name, scale)} or None])."""
+    from . import lora as _lora
+    loaded = _lora.loras(tools[1]) if tools is not None else []
+
+    def entry(value, what):
+        e = _lora.lora_entry(value, what)
+        if e[0] not in loaded:
+            raise ValueError("%s: LoRA adapter %r is not loaded on the UNet of preloaded_utils (loaded: %s); pww_hip.lora.load_lora(unet, source, name) "
+                             "loads one" % (what, e[0], loaded))
+        return e
+    g = None if lora is None else entry(lora, "lora")
+    n = n_requests if n_requests is not None else 1
+    if isinstance(region_loras, (list, tuple)):
+        if n_requests is None:
+            raise ValueError("region_loras must be a dict (a sequence of dicts is the batch form)")
+        if len(region_loras) != n_requests:
+            raise ValueError("region_loras has %d entries for %d requests" % (len(region_loras), n_requests))
+        per = list(region_loras)
+    else:
+        per = [region_loras] * n
+    prompts = list(region_prompts) if isinstance(region_prompts, (list, tuple)) else [region_prompts] * n
+    out = []
+    for rl, rp in zip(per, prompts):
+        if rl is None or (isinstance(rl, dict) and not rl):
+            out.append(None)
+            continue
+        if not isinstance(rl, dict):
+            raise ValueError("region_loras must be a dict {(r, g, b): \"name\"} or {(r, g, b): (\"name\", scale)} (got %r)" % type(rl).__name__)
+        colors = [e[0] for e in region_entries(rp)] if rp else []
+        d = {}
+        for color, value in rl.items():
+            rgb = _rgb_of(color)
+            if rgb in d:
+                raise ValueError("region_loras names colour %s twice" % (rgb,))
+            if rgb not in colors:
+                raise ValueError("region_loras: colour %s is not a key of the request's region_prompts (%s)" % (rgb, colors))
+            d[rgb] = entry(value, "region_loras[%s]" % (rgb,))
+        out.append(d)
+    if g is None and not any(out):
+        return None
+    return g, out
+
+
 def encode_region_prompts(text_encoder, tokenizer, device, color_map_rgb, region_prompts, guidance_scale, like, dtype=None,
                           region_base_weight=0.0, region_feather=0.0):
     """One request's region prompts -> its plan for the sampler:

@@ -1181,3 +1181,68 @@ def linear(x, weight, bias=None, residual=None, geglu=False, tile_n=0, splitk=0,
     with torch.cuda.device(x.device):
         _lib.check(lib.pww_linear_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(out), ctypes.byref(d), _ptr(ws), nbytes, _stream()), "pww_linear_fwd", lib)
     return out
+
+
+# ---- the per-row low-rank update of unmerged LoRA adapters (csrc/pww_lora.hip, libpww_hip_lora.so) -------------------------------------
+def lora_update_torch(y, x, A, B, row_adapter, row_scale, n_seg):
+    """pww_lora_fwd's formula from stock torch ops, in place on y (any device, any float dtype): per adapter and segment two matmuls (the
+    first one's output is a tensor of y's dtype, i.e. rounded once) and the scaled add in at least fp32, rounded once. The rows are selected
+    by a mask instead of gathered -- no shape depends on the assignment, so this too is legal under stream capture -- and a row without an
+    adapter (or with scale 0) keeps its bits."""
+    R, ns = y.shape[0], y.shape[-1] // n_seg
+    ra, rs = row_adapter[:R].reshape(R, 1, 1), row_scale[:R].reshape(R, 1, 1)
+    wide = torch.promote_types(y.dtype, torch.float32)
+    for i in range(A.shape[0]):
+        on = (ra == i) & (rs != 0)
+        for g in range(n_seg):
+            u = torch.matmul(torch.matmul(x, A[i, g].t()), B[i, g].t())
+            seg = y[..., g * ns:(g + 1) * ns]
+            seg.copy_(torch.where(on, (seg.to(wide) + rs.to(wide) * u.to(wide)).to(y.dtype), seg))
+    return y
+
+
+def lora_takes(y, x, A, B, n_seg):
+    """True when pww_lora_fwd runs this update -- everything the library would answer PWW_ENOTSUP or PWW_EINVAL to is declined here."""
+    if not (torch.is_tensor(y) and y.is_cuda and y.dtype in _DT and y.dim() == 3 and x.dim() == 3 and x.dtype == y.dtype == A.dtype == B.dtype
+            and x.is_cuda and A.is_cuda and B.is_cuda and A.is_contiguous() and B.is_contiguous() and A.dim() == 4 and B.dim() == 4):
+        return False
+    (R, T, N), K, (n, seg, rank, _) = y.shape, x.shape[-1], A.shape
+    if not (tuple(x.shape[:2]) == (R, T) and seg == n_seg and 1 <= n_seg <= _lib.LORA_MAX_SEGMENTS and 1 <= n <= _lib.LORA_MAX_ADAPTERS and A.shape[3] == K
+            and N % n_seg == 0 and tuple(B.shape) == (n, n_seg, N // n_seg, rank) and rank in (32, 64, 96, 128) and K % 32 == 0 and (N // n_seg) % 16 == 0
+            and 1 <= R <= 65535 and T >= 1):
+        return False
+    for t, w in ((x, K), (y, N)):
+        rs, ts = (T * t.stride(1) if R == 1 else t.stride(0)), t.stride(1)
+        if t.stride(2) != 1 or ts < w or rs < T * ts or rs % 8 or ts % 8 or t.data_ptr() % 16 or R * rs >= 2 ** 31:
+            return False
+    return A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0 and A.numel() < 2 ** 31 and B.numel() < 2 ** 31
+
+
+def lora_update(y, x, layer_stack, state, n_seg):
+    """y += s (x A^T) B^T per row, in place: y [R, T, N] (a view of a wider buffer is fine), x [R, T, K], layer_stack = (A [n][n_seg][rank][K],
+    B [n][n_seg][N / n_seg][rank]) (lora.LoraLayer.stack), the row's adapter and scale from `state` (lora.LoraState: row_adapter / row_scale,
+    device arrays the launch reads when it RUNS). One launch of libpww_hip_lora.so where it takes the operands; anything else runs
+    lora_update_torch and is counted as declined (lora.stats())."""
+    from . import lora as _lora
+    A, B = layer_stack
+    if x.dtype != y.dtype:
+        x = x.to(y.dtype)
+    if A.dtype != y.dtype:      # (autocast: the projections ran in another dtype than the UNet's)
+        A, B = A.to(y.dtype), B.to(y.dtype)
+    if x.dim() == 3 and (x.stride(2) != 1 or x.stride(1) % 8 or (x.shape[0] > 1 and (x.stride(0) % 8 or x.stride(0) < x.shape[1] * x.stride(1))) or x.data_ptr() % 16):
+        x = x.contiguous()
+    state._ensure_rows()
+    if y.shape[0] > state.row_adapter.numel():
+        raise PwwHipError("lora_update: %d rows, the assignment holds %d" % (y.shape[0], state.row_adapter.numel()))
+    if not lora_takes(y, x, A, B, n_seg):
+        _lora._stats["declined"] += 1
+        return lora_update_torch(y, x, A, B, state.row_adapter, state.row_scale, n_seg)
+    (R, T, N), K = y.shape, x.shape[-1]
+    d = _lib.LoraDesc(ctypes.sizeof(_lib.LoraDesc), _DT[y.dtype], R, T, K, N, n_seg, A.shape[2], A.shape[0], 0,
+                      T * x.stride(1) if R == 1 else x.stride(0), x.stride(1), T * y.stride(1) if R == 1 else y.stride(0), y.stride(1))
+    lib = _lib.load_lora()
+    with torch.cuda.device(y.device):
+        _lib.check(lib.pww_lora_fwd(_ptr(x), _ptr(A), _ptr(B), _ptr(state.row_adapter), _ptr(state.row_scale), _ptr(y), ctypes.byref(d), _stream()),
+                   "pww_lora_fwd", lib)
+    _lora._stats["kernel"] += 1
+    return y

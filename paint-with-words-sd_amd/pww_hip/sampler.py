@@ -14,6 +14,8 @@ Three execution modes over the SAME arithmetic:
             weight_function produces -- live in device words (attention.CoeffSlots) that the host
             rewrites before each replay. A weight function that is not of the form
             c * w * reduce(qk) bakes sigma into torch ops; the sampler then keeps one graph per step.
+LoRA adapters (pww_hip/lora.py) are chosen per row by two device arrays of the UNet's LoraState, written in place here: once per request in
+"folded" / "graph" (before the K|V projections are refreshed: they are adapted too), before every batch-1 call in "eager".
 Region prompts (a full prompt per colour, `regions=`) add K rows per image in each of the three: K more batch-1 calls in "eager", rows
 [base x n, region 1 x n, ..., region K x n, uncond x n] in "folded" / "graph" (_fold_regions), and the per-pixel blend of
 ops.region_combine where classifier-free guidance is combined otherwise.
@@ -22,6 +24,7 @@ import torch
 
 from . import ops
 from . import attnmaps
+from . import lora as _lora
 from .attention import install, refresh_kv_cache, refresh_orig_cache, ROW_GATE, KV_CACHE, COEFF_SLOTS, CoeffSlots, COMPACT_W, COMPACT_IDX, GATED_ROWS, COND_ROWS, BIAS_COLS, ATTN_RECORDER
 from .conditioning import PwWContext
 
@@ -363,6 +366,8 @@ class PwWSampler:
         self._request_folded = None
         self._scratch_modules = None
         self._errors = ops.FusedErrorWatch()
+        self._lora = None                # the UNet's lora.LoraState while adapters are loaded (looked up per request)
+        self._lora_calls = None          # eager mode: the one-row assignment of every batch-1 call of the request, [class * n + image]
         self.handoff_pending = False     # the last request issued launches with an in-kernel hand-off (PWW_QPROJ_STAT=0 / shapes the
                                          # to_q GEMM does not cover): its latents must not reach a caller before check_errors() has looked
 
@@ -376,6 +381,8 @@ class PwWSampler:
         # (recording attention maps on / off, per layer or not, is geometry too: the captured graph holds the probabilities launches or it does not)
         sig = (tuple(latents.shape), tensor_sig(folded), tuple(sorted((k, v) for k, v in folded.items() if isinstance(v, int) and not isinstance(v, bool))),
                None if rec is None else ("attention maps", rec.per_layer))
+        if self._lora is not None:      # LoRA launches are part of the graph: with which padded rank, over which stacks -- not for which rows
+            sig = sig + (self._lora.signature(),)
         self._request_folded = folded
         if sig != self._graph_sig:
             self._graphed.reset()
@@ -418,11 +425,12 @@ class PwWSampler:
 
     @torch.no_grad()
     def sample(self, cond, uncond, latents, timesteps, guidance_scale, weight_function, extra_channels=None,
-               on_step=None, negative_strength=1.0, regions=None):
+               on_step=None, negative_strength=1.0, regions=None, lora_rows=None):
         """cond / uncond: the two context dicts of the PwW protocol, or one dict per image (per-image prompts / maps).
         regions: None, or the region prompts of the request -- one plan of conditioning.encode_region_prompts or one per image: K more rows
         per image, blended per latent pixel (ops.region_combine) where guidance is combined otherwise.
         An unconditional dict that carries weight maps (negative regions) is evaluated with `negative_strength * weight_function`.
+        lora_rows: None (no row has an adapter), or lora.row_plan's (adapters, scales) for the rows [base x n, region 1 x n, ..., uncond x n].
         latents: [n_images, C, h, w] already scaled by init_noise_sigma (or noised for img2img).
         extra_channels: inpaint's cat([mask, masked_image_latents]) ([n or 1, 5, h, w]) or None."""
         sch, unet, dev = self.scheduler, self.unet, latents.device
@@ -441,6 +449,21 @@ class PwWSampler:
                                  % (sorted({tuple(p["masks"].shape[-2:]) for p in plans}), tuple(latents.shape[-2:])))
             stack = lambda key: torch.stack([p[key] for p in plans], dim=0).to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
             blend = {"plans": plans, "K": len(plans[0]["contexts"]), "masks": stack("masks"), "weights": stack("weights"), "scales": stack("scales")}
+        self._lora = _lora.state_of(unet)
+        if self._lora is not None and not self._lora.adapters:
+            self._lora = None
+        self._lora_calls = None
+        if self._lora is None and lora_rows is not None:
+            raise ValueError("lora_rows without a loaded LoRA adapter")
+        if self._lora is not None:
+            rows = ((blend["K"] if blend else 0) + 2) * n
+            adapters, scales = lora_rows if lora_rows is not None else ([-1] * rows, [0.0] * rows)
+            if len(adapters) != rows or len(scales) != rows:
+                raise ValueError("lora_rows: %d adapters / %d scales for %d rows" % (len(adapters), len(scales), rows))
+            if self.mode == "eager":
+                self._lora_calls = [self._lora.device_rows([a], [s]) for a, s in zip(adapters, scales)]
+            else:       # (before _static_context: it refreshes the cached K|V projections, which are adapted per row)
+                self._lora.assign(self._lora.device_rows(adapters, scales))
         if self.mode == "eager":   # per-request caches of the fused K|V projections (prompt constant over the steps)
             for d in conds + unconds + ([c for p in blend["plans"] for c in p["contexts"]] if blend else []):
                 d.setdefault(KV_CACHE, {}).clear()
@@ -476,6 +499,7 @@ class PwWSampler:
         # eager mode: per image, what its unconditional dict is evaluated with (one with weight maps of its own: negative regions)
         uncond_functions = [negative_function if _has_negative_maps(u) else zero_function for u in unconds] if folded is None else None
         K = blend["K"] if blend is not None else 0
+        calls = self._lora_calls        # eager mode with LoRA adapters loaded: every batch-1 call has its own one-row assignment
         for i, t in enumerate(timesteps):
             sigma, _ = self._sigma_and_index(i, t)
             x = sch.scale_model_input(latents, t)
@@ -487,12 +511,18 @@ class PwWSampler:
                     conds[j].update({"SIGMA": sigma, "WEIGHT_FUNCTION": weight_function})
                     if rec is not None:
                         rec.row = j
+                    if calls is not None:
+                        self._lora_call(calls[j], conds[j], n)
                     eps_c.append(unet(x[j:j + 1], t, encoder_hidden_states=conds[j]).sample)
                     for k in range(K):     # the region prompts: plain cross-attention, like the unconditional pass
                         ctx = blend["plans"][j]["contexts"][k]
                         ctx.update({"SIGMA": sigma, "WEIGHT_FUNCTION": zero_function})
+                        if calls is not None:
+                            self._lora_call(calls[(k + 1) * n + j], ctx, n)
                         eps_r[k].append(unet(x[j:j + 1], t, encoder_hidden_states=ctx).sample)
                     unconds[j].update({"SIGMA": sigma, "WEIGHT_FUNCTION": uncond_functions[j]})
+                    if calls is not None:
+                        self._lora_call(calls[(K + 1) * n + j], unconds[j], n)
                     eps_u.append(unet(x[j:j + 1], t, encoder_hidden_states=unconds[j]).sample)
                 eps_c, eps_u = torch.cat(eps_c), torch.cat(eps_u)
                 out = torch.cat([eps_c] + [torch.cat(r) for r in eps_r] + [eps_u]) if K else None
@@ -526,6 +556,13 @@ class PwWSampler:
             self._scratch_modules = [m for m in unet.modules() if m.__class__.__name__ in ("CrossAttention", "Attention")]
         self.handoff_pending = self._errors.post(self._scratch_modules)
         return latents
+
+    def _lora_call(self, rows, context, n):
+        """Eager mode: the one-row assignment of the batch-1 call about to be made. The dict's cached K|V projection is adapted with the
+        row's adapter; a dict that serves several images (each with its own assignment) forms it again per call."""
+        self._lora.assign(rows)
+        if n > 1:
+            context.get(KV_CACHE, {}).clear()
 
     def check_errors(self):
         """Wait for the requests issued so far and raise PwwHipError if a fused cross-attention hand-off of any of them timed out
