@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define PWW_VERSION 126 /* 0.1.26: the forms that were measured and not made a default moved to libpww_hip_experiments.so (section "experiments" below: pww_cross_attn_fwd_fused[_ex], pww_cross_fused_*_bytes, pww_cross_attn_fwd_parts_out, pww_cross_attn_out_supported); pww_has_experiments; 0.1.25: pww_cross_attn_fwd_parts_out / pww_cross_attn_out_supported (the C = 320 cross-attention layers with to_out + bias [+ residual] in the attention launch); 0.1.24: pww_qk_parts / pww_qk_parts_count (statistic partials over a finished Q; pww_cross_attn_fwd_parts takes the small one-block-per-workgroup kernel where it fits); 0.1.23: pww_group_norm_fwd / pww_group_norm_workspace_bytes, pww_add_layer_norm, pww_geglu, pww_bias_residual (norms and elementwise glue of the blocks that call the attention path); 0.1.22: pww_qproj_stat / pww_qproj_parts / pww_cross_attn_fwd_parts (score statistic formed in the to_q GEMM's epilogue), pww_mask_build_f32_levels, PWW_STAT_ALL; 0.1.21: pww_cross_opts_t.gated_images (was padding); 0.1.20: + pww_cross_attn_fwd_fused_ex / pww_cross_attn_fwd_stat_ex (pww_cross_opts_t: device-side coefficient word, bias column bound,
+#define PWW_VERSION 127 /* 0.1.27: pww_debug_last_attn_route (host-side report of the code object the general attention launch picked); 0.1.26: the forms that were measured and not made a default moved to libpww_hip_experiments.so (section "experiments" below: pww_cross_attn_fwd_fused[_ex], pww_cross_fused_*_bytes, pww_cross_attn_fwd_parts_out, pww_cross_attn_out_supported); pww_has_experiments; 0.1.25: pww_cross_attn_fwd_parts_out / pww_cross_attn_out_supported (the C = 320 cross-attention layers with to_out + bias [+ residual] in the attention launch); 0.1.24: pww_qk_parts / pww_qk_parts_count (statistic partials over a finished Q; pww_cross_attn_fwd_parts takes the small one-block-per-workgroup kernel where it fits); 0.1.23: pww_group_norm_fwd / pww_group_norm_workspace_bytes, pww_add_layer_norm, pww_geglu, pww_bias_residual (norms and elementwise glue of the blocks that call the attention path); 0.1.22: pww_qproj_stat / pww_qproj_parts / pww_cross_attn_fwd_parts (score statistic formed in the to_q GEMM's epilogue), pww_mask_build_f32_levels, PWW_STAT_ALL; 0.1.21: pww_cross_opts_t.gated_images (was padding); 0.1.20: + pww_cross_attn_fwd_fused_ex / pww_cross_attn_fwd_stat_ex (pww_cross_opts_t: device-side coefficient word, bias column bound,
                            compact bias), pww_debug_timeline (0.1.11: pww_profile_*; 0.1.10: fused cross-attention, blur, resize, inpaint prep) */
 
 #define PWW_OK 0
@@ -491,6 +491,20 @@ void pww_profile_reset(void);
  * [3] finished on the lazy-reference path with the EXACT scale (fp16: a row's logits passed the magnitude guard on the way; no second pass).
  * NULL switches it off (the default). Process-wide, like pww_debug_timeline; bench.py reports the counts of its hot-logit rows. */
 void pww_debug_path_counts(void *device_buffer);
+
+/* Test aid (version >= 127): which code object the general attention launch (pww_self_attn_fwd, pww_cross_attn_fwd, pww_cross_attn_fwd_stat[_ex])
+ * picked on its last call from THIS thread. Host bookkeeping only: nothing is read from or handed to the device. Copies the first
+ * min(n, PWW_ROUTE_FIELDS) int32 fields to `out` and returns PWW_ROUTE_FIELDS (PWW_EINVAL for a null buffer); the fields, in order:
+ *   kind (PWW_ROUTE_*; 0 before the thread's first launch), KS (16-column K slabs of the head-dim class), DT (32-row V^T tiles), NW (row
+ *   groups = waves per key group), KG (key groups), NSUB (64-key sub-tiles per stage), HAS_BIAS, ROWSUM_MFMA (the softmax denominator comes
+ *   from the ones column of V), RF (range-free softmax). The tests assert the route a shape was chosen to reach (tests/attn_route_cases.py). */
+#define PWW_ROUTE_FIELDS 9
+#define PWW_ROUTE_NONE 0
+#define PWW_ROUTE_GENERAL 1   /* attn_fwd_kernel, one key group */
+#define PWW_ROUTE_KSPLIT 2    /* attn_fwd_kernel, NW row groups x KG key groups */
+#define PWW_ROUTE_FOLD 3      /* attn_fwd_fold_kernel (d = 8 / 24 / 40) */
+#define PWW_ROUTE_KSPLIT1 4   /* attn_ksplit1_kernel (experiments library) */
+int pww_debug_last_attn_route(int32_t *out, int n);
 
 /*
  * Phase time stamps of the attention kernels (debug / measurement aid). After pww_debug_timeline(buf, bytes) every attention

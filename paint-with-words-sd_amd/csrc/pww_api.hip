@@ -155,6 +155,12 @@ size_t debug_timeline_bytes() { std::lock_guard<std::mutex> lock(g_prof_mutex); 
 // ---- path counters of the folded-reference self-attention kernel (pww_debug_path_counts): { range-free, lazy, exact } workgroups
 static unsigned *g_path_counts = nullptr;
 unsigned *debug_path_counts() { std::lock_guard<std::mutex> lock(g_prof_mutex); return g_path_counts; }
+// ---- route report of the general attention launch (pww_debug_last_attn_route): what the calling thread's last launch helper picked
+static thread_local int32_t g_attn_route[PWW_ROUTE_FIELDS] = {};
+void record_attn_route(int kind, int ks, int dt, int nw, int kg, int nsub, bool has_bias, bool rowsum_mfma, bool rf) {
+    const int32_t r[PWW_ROUTE_FIELDS] = {kind, ks, dt, nw, kg, nsub, has_bias, rowsum_mfma, rf};
+    memcpy(g_attn_route, r, sizeof(r));
+}
 
 int attn_fwd(const void *q, const void *k, const void *v, void *o, const float *bias, const float *bias_coeff,
              const pww_attn_desc_t *d, hipStream_t stream, const double *stats = nullptr, int stat_kind = PWW_STAT_NONE,
@@ -310,6 +316,12 @@ int pww_mask_build_f32_levels(const float *masks, int32_t H, int32_t W, int32_t 
 void pww_debug_path_counts(void *device_buffer) {
     std::lock_guard<std::mutex> lock(pww::g_prof_mutex);
     pww::g_path_counts = static_cast<unsigned *>(device_buffer);
+}
+
+int pww_debug_last_attn_route(int32_t *out, int n) {
+    if (!out || n < 0) { pww::set_error("pww_debug_last_attn_route: null buffer or negative count"); return PWW_EINVAL; }
+    for (int i = 0; i < n && i < PWW_ROUTE_FIELDS; ++i) out[i] = pww::g_attn_route[i];
+    return PWW_ROUTE_FIELDS;
 }
 
 void pww_debug_timeline(void *device_buffer, size_t bytes) {

@@ -1010,8 +1010,10 @@ static int launch_attn_rs(const AttnParams &p, hipStream_t stream) {
 #if PWW_EXPERIMENTS      // PWW_DEBUG=attn_rf=0: the running-maximum form of the same launches (A/B; a second instantiation per shape class)
     auto kern = (CAN_RF && rf_mode() == 1) ? attn_fwd_kernel<T, KS, DT, NW, NSUB, 1, HAS_BIAS, ROWSUM_MFMA, CAN_RF>
                                            : attn_fwd_kernel<T, KS, DT, NW, NSUB, 1, HAS_BIAS, ROWSUM_MFMA, false>;
+    record_attn_route(PWW_ROUTE_GENERAL, KS, DT, NW, 1, NSUB, HAS_BIAS, ROWSUM_MFMA, CAN_RF && rf_mode() == 1);
 #else
     auto kern = attn_fwd_kernel<T, KS, DT, NW, NSUB, 1, HAS_BIAS, ROWSUM_MFMA, CAN_RF>;
+    record_attn_route(PWW_ROUTE_GENERAL, KS, DT, NW, 1, NSUB, HAS_BIAS, ROWSUM_MFMA, CAN_RF);
 #endif
     if (lds > 64 * 1024) {
         static thread_local bool done = false;
@@ -1038,6 +1040,7 @@ static int launch_attn_ksplit(const AttnParams &p, hipStream_t stream) {
     static_assert(lds <= 160 * 1024, "stage buffers / merge records of the key-split workgroup");
     const int qblocks = (p.N + NW * 32 - 1) / (NW * 32);
     auto kern = attn_fwd_kernel<T, KS, DT, NW, NSUB, KG, false, ROWSUM_MFMA>;
+    record_attn_route(PWW_ROUTE_KSPLIT, KS, DT, NW, KG, NSUB, false, ROWSUM_MFMA, false);
     static thread_local bool done = false;
     if (!done) {
         if (check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
@@ -1064,6 +1067,7 @@ static int launch_attn_ksplit1(const AttnParams &p, hipStream_t stream) {
     const int qblocks = (p.N + NW * 32 - 1) / (NW * 32);
     if (p.H > 65535 || p.B > 65535) { set_error("attn_fwd: more than 65535 heads or images"); return PWW_EINVAL; }
     auto kern = attn_ksplit1_kernel<T, KS, DT, NW, KG, RSM>;
+    record_attn_route(PWW_ROUTE_KSPLIT1, KS, DT, NW, KG, KG, false, RSM, false);
     static thread_local bool done = false;
     if (!done) {
         if (check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute"))
@@ -1093,6 +1097,7 @@ static int launch_attn_fold(const AttnParams &p, hipStream_t stream) {
     constexpr size_t lds = 2 * 2 * (KTile<KS>::BYTES + VTile<DT>::BYTES);
     const int qblocks = (p.N + NW * 32 - 1) / (NW * 32);
     auto kern = attn_fwd_fold_kernel<T, KS, DT, NW>;
+    record_attn_route(PWW_ROUTE_FOLD, KS, DT, NW, 1, 2, false, true, RangeFree<T>::value);   // (two sub-tiles per stage; the row sum always comes from the ones column)
     if (lds > 64 * 1024) {
         static thread_local bool done = false;
         if (!done) {

@@ -90,6 +90,10 @@ bool profile_take(hipEvent_t *start, hipEvent_t *stop, hipStream_t stream);
 unsigned long long *debug_timeline();
 size_t debug_timeline_bytes();
 
+// Route report (pww_debug_last_attn_route): the launch helpers of the general attention launch (pww_attn_kernel.h) note, per thread and on
+// the host alone, which code object they are about to launch. Kernel kinds: include/pww_hip.h, PWW_ROUTE_*.
+void record_attn_route(int kind, int ks, int dt, int nw, int kg, int nsub, bool has_bias, bool rowsum_mfma, bool rf);
+
 // Launch of an attention-class kernel. An armed launch goes through hipExtLaunchKernelGGL, which stamps the dispatch's own
 // start / end device timestamps into the two events: the duration rocprofv3 reports for the kernel, free of host latency and of
 // the gap between dispatches that an event pair AROUND a launch includes.

@@ -25,7 +25,7 @@ REGIONS_LIB_PATH = os.environ.get("PWW_HIP_REGIONS_LIB", os.path.join(_HERE, "li
 LORA_LIB_PATH = os.environ.get("PWW_HIP_LORA_LIB", os.path.join(_HERE, "libpww_hip_lora.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
-MIN_VERSION = 126        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
+MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
 DTYPE_F16, DTYPE_BF16 = 0, 1
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 ACT_NONE, ACT_SILU = 0, 1
@@ -37,6 +37,7 @@ EXPORTS = ("pww_version", "pww_has_experiments", "pww_last_error", "pww_device_a
            "pww_cross_attn_fwd_stat", "pww_cross_attn_fwd_stat_ex",
            "pww_qk_reduce", "pww_mask_build", "pww_mask_build_rgb", "pww_mask_build_f32", "pww_resize_tokens", "pww_gauss_blur", "pww_inpaint_prep", "pww_cfg_combine", "pww_store_f32",
            "pww_workspace_bytes", "pww_profile_arm", "pww_profile_elapsed_us", "pww_profile_reset", "pww_debug_timeline", "pww_debug_path_counts",
+           "pww_debug_last_attn_route",
            "pww_qproj_stat", "pww_qproj_parts", "pww_cross_attn_fwd_parts", "pww_mask_build_f32_levels", "pww_qk_parts", "pww_qk_parts_count",
            "pww_group_norm_fwd", "pww_group_norm_workspace_bytes", "pww_add_layer_norm", "pww_add_layer_norm_bias", "pww_geglu", "pww_bias_residual",
            "pww_conv3x3_workspace_bytes", "pww_conv3x3_fwd", "pww_cross_attn_probs")
@@ -200,6 +201,8 @@ def _bind(lib, experiments):
     lib.pww_debug_timeline.restype = None
     lib.pww_debug_path_counts.argtypes = [vp]
     lib.pww_debug_path_counts.restype = None
+    lib.pww_debug_last_attn_route.argtypes = [ctypes.POINTER(i32), ctypes.c_int]
+    lib.pww_debug_last_attn_route.restype = ctypes.c_int
     lib.pww_qk_reduce.argtypes = [vp, vp, ctypes.POINTER(AttnDesc), vp, vp, ctypes.c_size_t, vp]
     lib.pww_mask_build.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.pww_mask_build_rgb.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp]

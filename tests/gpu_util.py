@@ -49,6 +49,31 @@ def uninstall_all():
         del CrossAttention.__call__
 
 
+def path_counts(fn, device):
+    """fn() under pww_debug_path_counts: its result, and the workgroups of the folded-reference self-attention kernel per path."""
+    import ctypes
+    from pww_hip import _lib
+    lib = _lib.load()
+    counts = torch.zeros(4, dtype=torch.int32, device=device)
+    lib.pww_debug_path_counts(ctypes.c_void_p(counts.data_ptr()))
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+    finally:
+        lib.pww_debug_path_counts(None)
+    c = counts.tolist()
+    return out, {"fast": c[0], "lazy": c[1], "raw": c[3], "exact": c[2]}
+
+
+def last_attn_route():
+    """pww_debug_last_attn_route: the (kind, KS, DT, NW, KG, NSUB, HAS_BIAS, ROWSUM_MFMA, RF) record of this thread's last general attention launch."""
+    import ctypes
+    from pww_hip import _lib
+    rec = (ctypes.c_int32 * 9)()
+    assert _lib.load().pww_debug_last_attn_route(rec, 9) == 9
+    return tuple(rec)
+
+
 def rel_l2(a, b):
     a = a.detach().double().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, np.float64)
     b = b.detach().double().cpu().numpy() if torch.is_tensor(b) else np.asarray(b, np.float64)

@@ -40,7 +40,7 @@ def test_probs_export_layout_and_validation_without_a_device():
     from pww_hip import _lib as L
     lib = L.load()
     assert "pww_cross_attn_probs" in L.EXPORTS and hasattr(lib, "pww_cross_attn_probs")
-    assert lib.pww_version() == 126
+    assert lib.pww_version() == 127
     # uint32 size, int32 images, int32 accumulate, float weight, int64 out_stride[2]
     assert ctypes.sizeof(L.ProbsDesc) == 32
     assert (L.ProbsDesc.images.offset, L.ProbsDesc.accumulate.offset, L.ProbsDesc.weight.offset, L.ProbsDesc.out_stride.offset) == (4, 8, 12, 16)

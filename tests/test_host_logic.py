@@ -31,7 +31,7 @@ def test_library_loads_and_exports_every_declared_symbol(built_lib):
         assert hasattr(raw, name), name
     for name in moved:
         assert not hasattr(raw, name), "%s belongs to libpww_hip_experiments.so" % name
-    assert lib.pww_version() == 126 and lib.pww_has_experiments() == 0 and not _lib.has_experiments()
+    assert lib.pww_version() == 127 and lib.pww_has_experiments() == 0 and not _lib.has_experiments()
     assert lib.pww_last_error() == b"" or isinstance(lib.pww_last_error(), bytes)
     assert lib.pww_workspace_bytes(None) == 0
     assert os.path.getsize(built_lib) <= 6 * 1024 * 1024, "the product library grew past 6 MB: %d bytes" % os.path.getsize(built_lib)
@@ -45,7 +45,7 @@ def test_experiments_library_is_a_superset(experiments_lib):
     for name in _lib.EXPORTS + _lib.EXPERIMENT_EXPORTS:
         assert hasattr(raw, name), name
     raw.pww_has_experiments.restype = ctypes.c_int
-    assert raw.pww_has_experiments() == 1 and raw.pww_version() == 126
+    assert raw.pww_has_experiments() == 1 and raw.pww_version() == 127
     assert _lib.load_experiments().pww_has_experiments() == 1
 
 

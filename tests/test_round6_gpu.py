@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import pww_cases as cases
+from gpu_util import path_counts as _path_counts
 from oracle import pww_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -144,21 +145,6 @@ def test_half_rounded_statistic_delta(gpu_device, shape, dtype):
 
 
 # ---- the fp16 d = 40 launch on hot logits ------------------------------------------------------------------------
-
-def _path_counts(fn, device):
-    import ctypes
-    from pww_hip import _lib
-    lib = _lib.load()
-    counts = torch.zeros(4, dtype=torch.int32, device=device)
-    lib.pww_debug_path_counts(ctypes.c_void_p(counts.data_ptr()))
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        lib.pww_debug_path_counts(None)
-    c = counts.tolist()
-    return out, {"fast": c[0], "lazy": c[1], "raw": c[3], "exact": c[2]}
-
 
 @pytest.mark.parametrize("std,expect", [(0.5, "fast"), (4.0, "lazy"), (5.0, "lazy")])
 def test_fp16_hot_rows_leave_the_range_free_mode_not_the_fast_path(gpu_device, std, expect):
