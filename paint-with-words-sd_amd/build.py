@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Seven libraries come out of the same sources:
+Eight libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
                               measured and not made a default (include/pww_hip.h, section "experiments"). Built by the tests / tools that
@@ -18,6 +18,8 @@ Seven libraries come out of the same sources:
                                 linear    linear layers with a bias / residual / GEGLU epilogue
                                 regions   region prompts: the region masks at latent resolution and the per-pixel blend of the noise predictions
                                 lora      unmerged LoRA adapters chosen per batch row: the low-rank update behind the attention projections
+                              and SIDE_LIBS_CONV, the same kind of row for the side libraries of the convolutions:
+                                convtail  conv2 of a ResnetBlock2D with the block's 1 x 1 shortcut as further K-slabs (csrc/pww_conv_tail.hip)
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -49,12 +51,18 @@ SIDE_LIBS = {
     "regions": ("pww_regions.hip", [], "region masks and the per-pixel blend of the noise predictions"),
     "lora": ("pww_lora.hip", [], "the per-row low-rank update of unmerged LoRA adapters"),
 }
+# (a table of its own: SIDE_LIBS is, key for key, the loader's SIDE + SIDE_MORE, and the loader keeps this library in SIDE_CONV)
+SIDE_LIBS_CONV = {
+    "convtail": ("pww_conv_tail.hip", [], "conv2 of a ResnetBlock2D with the 1 x 1 shortcut as further K-slabs"),
+}
+ALL_SIDE_LIBS = {**SIDE_LIBS, **SIDE_LIBS_CONV}
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
 HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_attn_kernel.h", "pww_cross_tile.h", "pww_cross_kernel.h", os.path.join(REPO, "include", "pww_hip.h")]
-SIDE_PATHS = {n: os.path.join(HERE, "pww_hip", "libpww_hip_%s.so" % n) for n in SIDE_LIBS}
-SIDE_UNITS = {n: [(v[0], SIDE_FLAGS, "")] for n, v in SIDE_LIBS.items()}     # (as in UNITS)
+SIDE_PATHS = {n: os.path.join(HERE, "pww_hip", "libpww_hip_%s.so" % n) for n in ALL_SIDE_LIBS}
+SIDE_UNITS = {n: [(v[0], SIDE_FLAGS, "")] for n, v in ALL_SIDE_LIBS.items()}     # (as in UNITS)
 LIB_LONG, LIB_SCOPE, LIB_LINEAR, LIB_REGIONS, LIB_LORA = (SIDE_PATHS[n] for n in ("long", "scope", "linear", "regions", "lora"))
 LONG_UNITS, SCOPE_UNITS, LINEAR_UNITS, REGIONS_UNITS, LORA_UNITS = (SIDE_UNITS[n] for n in ("long", "scope", "linear", "regions", "lora"))
+LIB_CONVTAIL, CONVTAIL_UNITS = SIDE_PATHS["convtail"], SIDE_UNITS["convtail"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
 # into SGPRs by the dispatcher instead of fetched by the wave's first s_load (gfx950 supports kernarg preload; the compiler keeps a compatibility
@@ -122,8 +130,8 @@ def build_experiments(force=False, verbose=False):
 
 
 def build_side(name, force=False, verbose=False):
-    """libpww_hip_<name>.so, one of SIDE_LIBS (include/pww_hip_<name>.h)."""
-    unit, headers, _ = SIDE_LIBS[name]
+    """libpww_hip_<name>.so, one of SIDE_LIBS / SIDE_LIBS_CONV (include/pww_hip_<name>.h)."""
+    unit, headers, _ = ALL_SIDE_LIBS[name]
     lib = SIDE_PATHS[name]
     deps = [os.path.join(CSRC, f) for f in [unit, "pww_common.h", "pww_side_host.h"] + headers] + [os.path.join(REPO, "include", h) for h in ("pww_hip.h", "pww_hip_%s.h" % name)] + [__file__]
     if not force and not _newer(lib, deps):
@@ -136,6 +144,7 @@ def build_scope(force=False, verbose=False): return build_side("scope", force, v
 def build_linear(force=False, verbose=False): return build_side("linear", force, verbose)  # noqa: E704
 def build_regions(force=False, verbose=False): return build_side("regions", force, verbose)  # noqa: E704
 def build_lora(force=False, verbose=False): return build_side("lora", force, verbose)  # noqa: E704
+def build_convtail(force=False, verbose=False): return build_side("convtail", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):
@@ -162,7 +171,7 @@ if __name__ == "__main__":
     force = "--force" in sys.argv
     print(build_lib(force=force, verbose=True))
     print(build_native_check(force=force))
-    for name in SIDE_LIBS:
+    for name in ALL_SIDE_LIBS:
         print(build_side(name, force=force, verbose=True))
     if "--experiments" in sys.argv:
         print(build_experiments(force=force, verbose=True))

@@ -23,6 +23,9 @@ LINEAR_LIB_PATH = os.environ.get("PWW_HIP_LINEAR_LIB", os.path.join(_HERE, "libp
 REGIONS_LIB_PATH = os.environ.get("PWW_HIP_REGIONS_LIB", os.path.join(_HERE, "libpww_hip_regions.so"))
 #   lora      unmerged LoRA adapters chosen per batch row (include/pww_hip_lora.h): ops.lora_update. Its spec is in SIDE_MORE below.
 LORA_LIB_PATH = os.environ.get("PWW_HIP_LORA_LIB", os.path.join(_HERE, "libpww_hip_lora.so"))
+#   convtail  conv2 of a ResnetBlock2D with the block's 1 x 1 shortcut as further K-slabs (include/pww_hip_convtail.h): ops.conv3x3_shortcut.
+#             Its spec is in SIDE_CONV below.
+CONVTAIL_LIB_PATH = os.environ.get("PWW_HIP_CONVTAIL_LIB", os.path.join(_HERE, "libpww_hip_convtail.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -74,6 +77,11 @@ REGIONS_MAX, REGIONS_MAX_PLANE, REGIONS_MAX_FEATHER = 8, 9216, 8.0      # PWW_RE
 LORA_EXPORTS = ("pww_lora_version", "pww_lora_last_error", "pww_lora_fwd")
 LORA_MIN_VERSION = 100
 LORA_MAX_ADAPTERS, LORA_MAX_RANK, LORA_MAX_SEGMENTS = 8, 128, 3      # PWW_LORA_MAX_* of the header
+
+
+# every symbol include/pww_hip_convtail.h declares for libpww_hip_convtail.so
+CONVTAIL_EXPORTS = ("pww_convtail_version", "pww_convtail_last_error", "pww_convtail_workspace_bytes", "pww_convtail_fwd")
+CONVTAIL_MIN_VERSION = 100
 
 
 class AttnDesc(ctypes.Structure):
@@ -136,6 +144,12 @@ class LoraDesc(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("R", ctypes.c_int32), ("T", ctypes.c_int32), ("K", ctypes.c_int32),
                 ("N", ctypes.c_int32), ("n_seg", ctypes.c_int32), ("rank", ctypes.c_int32), ("n_adapters", ctypes.c_int32), ("_pad", ctypes.c_int32),
                 ("x_row_stride", ctypes.c_int64), ("x_tok_stride", ctypes.c_int64), ("y_row_stride", ctypes.c_int64), ("y_tok_stride", ctypes.c_int64)]
+
+
+class ConvTailDesc(ctypes.Structure):
+    """struct pww_convtail_desc (3 x 3 convolution + 1 x 1 shortcut as one implicit GEMM; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("Cin", ctypes.c_int32), ("C2", ctypes.c_int32), ("Cout", ctypes.c_int32), ("tile_n", ctypes.c_int32), ("splitk", ctypes.c_int32)]
 
 
 class Region(ctypes.Structure):
@@ -316,16 +330,23 @@ SIDE_MORE = {
     "lora": dict(path="LORA_LIB_PATH", exports=LORA_EXPORTS, min_version=LORA_MIN_VERSION, missing_ok=False, needs="LoRA adapters on the native kernel need it", sigs={
         "pww_lora_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _P(LoraDesc), _vp], _int)}),
 }
+# the side libraries of the convolutions (build.py: SIDE_LIBS_CONV). missing_ok: the caller keeps the 1 x 1 GEMM + conv3x3 sequence, which
+# computes the same thing on this repository's own kernel
+SIDE_CONV = {
+    "convtail": dict(path="CONVTAIL_LIB_PATH", exports=CONVTAIL_EXPORTS, min_version=CONVTAIL_MIN_VERSION, missing_ok=True, needs="conv2 with the shortcut as K-slabs needs it", sigs={
+        "pww_convtail_workspace_bytes": ([_P(ConvTailDesc)], _sz),
+        "pww_convtail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(ConvTailDesc), _vp, _sz, _vp], _int)}),
+}
 _side = {}      # name -> loaded handle
 
 
 def side_spec(name):
-    """The table entry of a side library (SIDE or SIDE_MORE)."""
-    return SIDE[name] if name in SIDE else SIDE_MORE[name]
+    """The table entry of a side library (SIDE, SIDE_MORE or SIDE_CONV)."""
+    return SIDE[name] if name in SIDE else SIDE_MORE[name] if name in SIDE_MORE else SIDE_CONV[name]
 
 
 def load_side(name):
-    """libpww_hip_<name>.so of SIDE / SIDE_MORE, loaded once. A missing file returns None where the table says so (scope: the caller keeps the
+    """libpww_hip_<name>.so of SIDE / SIDE_MORE / SIDE_CONV, loaded once. A missing file returns None where the table says so (scope: the caller keeps the
     materialised route) and raises otherwise -- there is no second implementation to fall back to. A file that is there but stale, broken
     or short of an entry point raises. Every failure is a PwwHipError with the rebuild hint."""
     lib = _side.get(name)
@@ -381,6 +402,11 @@ def load_regions():
 def load_lora():
     lib = _side.get("lora")
     return lib if lib is not None else load_side("lora")
+
+
+def load_convtail():
+    lib = _side.get("convtail")
+    return lib if lib is not None else load_side("convtail")
 
 
 class experiments:

@@ -14,7 +14,8 @@ Installed per INSTANCE (``module.forward = ...``; ``nn.Module.__call__`` and its
   Blocks this restatement does not cover (``upsample`` / ``downsample`` inside the block, ``time_embedding_norm != "default"``, a nonlinearity
   other than SiLU) keep their own forward.
   The biases of ``conv1`` / ``conv2`` ride along as operands of the next fused op (``pre_bias`` of norm2, ``ops.bias_residual`` for the block's
-  output) instead of costing an add launch each.
+  output) instead of costing an add launch each. A block that changes its channel count runs ``conv_shortcut(x) + conv2(h)`` as ONE implicit
+  GEMM (``ops.conv3x3_shortcut``: the 1 x 1 shortcut as further K-slabs of conv2's kernel) where ``_conv_shortcut_route`` says so.
 * every other ``nn.GroupNorm`` of the model (``Transformer2DModel.norm``, ``conv_norm_out``) -- the same kernels without addend / activation.
 * ``BasicTransformerBlock`` -- ``attn(norm(h)) + h`` and the block's NEXT LayerNorm as one launch (``ops.add_layer_norm``); ``GEGLU`` --
   ``x * gelu(gate)`` as one launch behind its projection; 1 x 1 ``nn.Conv2d`` (``proj_in`` / ``proj_out`` / ``conv_shortcut``) on channels_last
@@ -42,6 +43,9 @@ CONV1X1_AS_LINEAR = os.environ.get("PWW_CONV1X1_AS_LINEAR", "1") != "0"  # A/B: 
 # "0": never; "force": every shape the kernel takes (tests, tools), whatever the table says
 LINEAR = os.environ.get("PWW_LINEAR", "1")
 CONV3X3 = os.environ.get("PWW_CONV3X3", "1") != "0"      # A/B: 3 x 3 convolutions on channels_last tensors on the HIP implicit-GEMM kernel
+# A/B: the 1 x 1 conv_shortcut of a ResnetBlock2D as further K-slabs of conv2's implicit GEMM (csrc/pww_conv_tail.hip); "0": the 1 x 1 GEMM
+# writes its tensor and conv2's epilogue reads it as the residual
+CONV_SHORTCUT = os.environ.get("PWW_CONV_SHORTCUT", "1") != "0"
 
 
 # ---- what the plug did with the calls it saw (a call the kernels decline must not go unnoticed) ----------------
@@ -49,8 +53,8 @@ CONV3X3 = os.environ.get("PWW_CONV3X3", "1") != "0"      # A/B: 3 x 3 convolutio
 # passes and while a hipGraph is captured (a replay runs no Python). `stats()` returns a copy, `reset_stats()` zeroes; the first decline of
 # a HIP half-precision tensor per (op, reason) also warns once -- under torch.autocast, the reference's own run mode, the whole plug steps
 # aside (autocast runs the norms in fp32) and that is worth knowing when a benchmark claims the fused blocks.
-_STATS = {k: [0, 0] for k in ("group_norm", "resnet_block", "transformer_block", "geglu", "conv1x1", "conv3x3", "linear")}
-_UNRATED = ("conv1x1", "conv3x3", "linear")
+_STATS = {k: [0, 0] for k in ("group_norm", "resnet_block", "transformer_block", "geglu", "conv1x1", "conv3x3", "linear", "conv_shortcut")}
+_UNRATED = ("conv1x1", "conv3x3", "linear", "conv_shortcut")
 _warned = set()
 
 
@@ -58,7 +62,8 @@ def stats():
     """{op: {"fused": n, "declined": n}} since the last reset_stats(), and the hit rate over the norm / elementwise ops (the 1 x 1
     and 3 x 3 convolutions are listed but not rated: an NCHW tensor keeps MIOpen's convolution by the caller's choice of memory format, and
     the UNet's conv_in / conv_out have channel counts the kernel has no tile for; `linear` counts the GEMMs that were offered to the HIP
-    linear kernel: "declined" ones run as the stock GEMM by the measured route table)."""
+    linear kernel: "declined" ones run as the stock GEMM by the measured route table; `conv_shortcut` counts the ResnetBlock2D calls that have
+    a conv_shortcut: "fused" ones ran it inside conv2's kernel, "declined" ones as the 1 x 1 GEMM in front of conv2)."""
     out = {k: {"fused": v[0], "declined": v[1]} for k, v in _STATS.items()}
     rated = [v for k, v in _STATS.items() if k not in _UNRATED]
     tot = sum(v[0] + v[1] for v in rated)
@@ -218,9 +223,12 @@ def _resnet_forward(self, *args, **kwargs):
     dropout = getattr(self, "dropout", None)
     if dropout is not None:
         h = dropout(h)
-    if getattr(self, "conv_shortcut", None) is not None:
-        input_tensor = self.conv_shortcut(input_tensor)
     scale = getattr(self, "output_scale_factor", 1.0)
+    shortcut = getattr(self, "conv_shortcut", None)
+    if shortcut is not None:
+        if _conv_shortcut_route(self, shortcut, h, input_tensor, fold, scale):
+            return ops.conv3x3_shortcut(h, self.conv2.weight, self.conv2.bias, input_tensor, shortcut.weight, shortcut.bias)        # conv2 and the shortcut: one GEMM
+        input_tensor = shortcut(input_tensor)
     if fold and input_tensor.dtype == h.dtype and input_tensor.shape == (h.shape[0], self.conv2.out_channels) + h.shape[2:] and _conv3x3_route(self.conv2, h):
         out = ops.conv3x3(h, self.conv2.weight, self.conv2.bias, residual=input_tensor)           # input + (conv2(h) + bias): one kernel
     elif fold and input_tensor.dtype == h.dtype and input_tensor.shape[1] % 8 == 0:
@@ -247,6 +255,27 @@ def _conv3x3_route(conv, x, upsample=False):
           and (conv.bias is None or conv.bias.dtype == x.dtype) and ops.conv3x3_takes(x, conv.weight, conv.stride[0], upsample)
           and (upsample or x.shape[0] * ((x.shape[2] - 1) // conv.stride[0] + 1) * ((x.shape[3] - 1) // conv.stride[0] + 1) < STOCK_FROM_ROWS))
     _STATS["conv3x3"][0 if ok else 1] += 1
+    return ok
+
+
+def _conv_shortcut_route(block, shortcut, h, x, fold, scale):
+    """Whether `conv_shortcut(x) + conv2(h)` of this ResnetBlock2D call runs as ONE implicit GEMM (ops.conv3x3_shortcut); counts the call
+    either way (not rated). It does when the shortcut is a plain 1 x 1 nn.Conv2d with a bias whose forward is its own or this plug's, x is
+    a channels_last tensor of the block's dtype, conv2 would take the HIP route with its bias folded, nothing is divided afterwards, and
+    the side library is there. A decline leaves today's sequence: the 1 x 1 GEMM, then conv2 with the residual in its epilogue."""
+    own = shortcut.__dict__.get("forward")
+    ok = (CONV_SHORTCUT and fold and scale == 1.0 and _is_conv1x1(shortcut) and shortcut.bias is not None
+          and (own is None or getattr(own, "__func__", None) is _conv1x1_forward) and not shortcut._forward_hooks and not shortcut._forward_pre_hooks
+          and torch.is_tensor(x) and x.dim() == 4 and x.dtype == h.dtype == shortcut.weight.dtype == shortcut.bias.dtype
+          and x.is_contiguous(memory_format=torch.channels_last)
+          and not (torch.is_grad_enabled() and (x.requires_grad or shortcut.weight.requires_grad))
+          and _is_conv3x3(block.conv2) and block.conv2.stride == (1, 1) and ops.conv3x3_shortcut_takes(h, block.conv2.weight, x, shortcut.weight)
+          and ops._lib.load_convtail() is not None)
+    if ok:
+        ok = _conv3x3_route(block.conv2, h)      # (last: it counts conv2's call under conv3x3, and the declined path asks it again)
+        if not ok:
+            _STATS["conv3x3"][1] -= 1
+    _STATS["conv_shortcut"][0 if ok else 1] += 1
     return ok
 
 

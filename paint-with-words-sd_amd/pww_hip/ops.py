@@ -1103,6 +1103,49 @@ def conv3x3(x, weight, bias=None, residual=None, stride=1, upsample=False, tile_
     return y
 
 
+# ---- conv2 of a ResnetBlock2D with the block's 1 x 1 shortcut as further K-slabs (csrc/pww_conv_tail.hip, libpww_hip_convtail.so) -------
+def conv3x3_shortcut_takes(h, conv2_weight, x, shortcut_weight):
+    """True when pww_convtail_fwd runs this call: what conv3x3_takes asks of (h, conv2_weight) at stride 1, and a channels_last x of h's
+    dtype, device, batch and size whose channel count C2 is a multiple of 64, with a dense [Cout, C2, 1, 1] (or [Cout, C2]) weight of that dtype."""
+    if not (conv3x3_takes(h, conv2_weight) and torch.is_tensor(x) and x.is_cuda and x.device == h.device and x.dim() == 4 and x.dtype == h.dtype
+            and torch.is_tensor(shortcut_weight) and shortcut_weight.dtype == h.dtype and shortcut_weight.device == h.device):
+        return False
+    w2 = _linear_weight(shortcut_weight)
+    B, C2, H, W = x.shape
+    return (w2 is not None and tuple(w2.shape) == (conv2_weight.shape[0], C2) and C2 % 64 == 0 and (B, H, W) == (h.shape[0], h.shape[2], h.shape[3])
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0 and B * H * W * C2 < 2 ** 31 // 4)
+
+
+def conv3x3_shortcut(h, conv2_weight, conv2_bias, x, shortcut_weight, shortcut_bias, tile_n=0, splitk=0):
+    """conv3x3(h, conv2_weight) + conv1x1(x, shortcut_weight) + conv2_bias + shortcut_bias for channels_last h ([B, Cin, H, W]) and x
+    ([B, C2, H, W]) -> channels_last [B, Cout, H, W]: ONE implicit GEMM over 9 Cin + C2 (+ a fold launch when K is split), the shortcut's
+    output never a tensor. fp32 accumulation, one rounding: T(acc + conv2_bias + shortcut_bias). tile_n / splitk: 0 = the library's choice."""
+    _require_gpu(h, conv2_weight, conv2_bias, x, shortcut_weight, shortcut_bias)
+    if not conv3x3_shortcut_takes(h, conv2_weight, x, shortcut_weight):
+        raise PwwHipError("conv3x3_shortcut: needs channels_last float16/bfloat16 h and x of one dtype, batch and size, channel counts multiples of 64, "
+                          "a 3 x 3 weight and a dense 1 x 1 weight of that dtype")
+    B, C, H, W = h.shape
+    Cout, C2 = conv2_weight.shape[0], x.shape[1]
+    w = _khwc_weight(conv2_weight)
+    w2 = _linear_weight(shortcut_weight)
+    biases = []
+    for name, b in (("conv2_bias", conv2_bias), ("shortcut_bias", shortcut_bias)):
+        if not torch.is_tensor(b) or b.dtype != h.dtype or tuple(b.shape) != (Cout,):
+            raise PwwHipError("conv3x3_shortcut: %s must be a %s [%d]" % (name, h.dtype, Cout))
+        biases.append(b.contiguous() if b.data_ptr() % 8 == 0 else b.clone(memory_format=torch.contiguous_format))
+    lib = _lib.load_convtail()
+    if lib is None:
+        raise PwwHipError("conv3x3_shortcut: libpww_hip_convtail.so is not built %s" % _lib._HINT)
+    d = _lib.ConvTailDesc(ctypes.sizeof(_lib.ConvTailDesc), _DT[h.dtype], B, H, W, C, C2, Cout, int(tile_n), int(splitk))
+    y = torch.empty((B, Cout, H, W), dtype=h.dtype, device=h.device, memory_format=torch.channels_last)
+    nbytes = int(lib.pww_convtail_workspace_bytes(ctypes.byref(d)))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=h.device) if nbytes else None
+    with torch.cuda.device(h.device):
+        _lib.check(lib.pww_convtail_fwd(_ptr(h), _ptr(w), _ptr(x), _ptr(w2), _ptr(biases[0]), _ptr(biases[1]), _ptr(y), ctypes.byref(d), _ptr(ws), nbytes,
+                                        _stream()), "pww_convtail_fwd", lib)
+    return y
+
+
 # ---- linear layers with the post-processing of the GEMM's output in its epilogue (csrc/pww_linear.hip, libpww_hip_linear.so) ------------
 def _linear_weight(weight):
     """[N, K] view of an nn.Linear weight or of a 1 x 1 conv weight ([N, K, 1, 1]), in place; None when it is neither or not dense."""
