@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Eight libraries come out of the same sources:
+Nine libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
                               measured and not made a default (include/pww_hip.h, section "experiments"). Built by the tests / tools that
@@ -20,6 +20,8 @@ Eight libraries come out of the same sources:
                                 lora      unmerged LoRA adapters chosen per batch row: the low-rank update behind the attention projections
                               and SIDE_LIBS_CONV, the same kind of row for the side libraries of the convolutions:
                                 convtail  conv2 of a ResnetBlock2D with the block's 1 x 1 shortcut as further K-slabs (csrc/pww_conv_tail.hip)
+                              and SIDE_LIBS_EXTRA, the open-ended home of every later side library:
+                                canvas    canvases larger than the UNet's window: the gather of the windows and the combine of their noise predictions
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -55,7 +57,12 @@ SIDE_LIBS = {
 SIDE_LIBS_CONV = {
     "convtail": ("pww_conv_tail.hip", [], "conv2 of a ResnetBlock2D with the 1 x 1 shortcut as further K-slabs"),
 }
-ALL_SIDE_LIBS = {**SIDE_LIBS, **SIDE_LIBS_CONV}
+# (the open-ended table: SIDE_LIBS and SIDE_LIBS_CONV are closed -- the loader's SIDE + SIDE_MORE and SIDE_CONV, key for key -- and every later
+# side library is a row here and in the loader's SIDE_EXTRA, whatever it is for)
+SIDE_LIBS_EXTRA = {
+    "canvas": ("pww_canvas.hip", [], "canvases larger than the UNet's window: the windows' gather and the combine of their noise predictions"),
+}
+ALL_SIDE_LIBS = {**SIDE_LIBS, **SIDE_LIBS_CONV, **SIDE_LIBS_EXTRA}
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
 HEADERS = ["pww_common.h", "pww_tile.h", "pww_attn_core.h", "pww_attn_kernel.h", "pww_cross_tile.h", "pww_cross_kernel.h", os.path.join(REPO, "include", "pww_hip.h")]
 SIDE_PATHS = {n: os.path.join(HERE, "pww_hip", "libpww_hip_%s.so" % n) for n in ALL_SIDE_LIBS}
@@ -63,6 +70,8 @@ SIDE_UNITS = {n: [(v[0], SIDE_FLAGS, "")] for n, v in ALL_SIDE_LIBS.items()}    
 LIB_LONG, LIB_SCOPE, LIB_LINEAR, LIB_REGIONS, LIB_LORA = (SIDE_PATHS[n] for n in ("long", "scope", "linear", "regions", "lora"))
 LONG_UNITS, SCOPE_UNITS, LINEAR_UNITS, REGIONS_UNITS, LORA_UNITS = (SIDE_UNITS[n] for n in ("long", "scope", "linear", "regions", "lora"))
 LIB_CONVTAIL, CONVTAIL_UNITS = SIDE_PATHS["convtail"], SIDE_UNITS["convtail"]
+LIB_CANVAS, CANVAS_UNITS = SIDE_PATHS["canvas"], SIDE_UNITS["canvas"]
+SIDE_PUBLIC_HEADERS = {"canvas": ["pww_hip_regions.h"]}       # include/ headers a side library's own header includes (besides pww_hip.h)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
 # into SGPRs by the dispatcher instead of fetched by the wave's first s_load (gfx950 supports kernarg preload; the compiler keeps a compatibility
@@ -71,8 +80,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
          "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
-# pww_mask.hip and pww_regions.hip restate fp32 formulas that must match a CPU restatement bit for bit: no FMA contraction.
-PER_FILE_FLAGS = {"pww_mask.hip": ["-ffp-contract=off"], "pww_regions.hip": ["-ffp-contract=off"]}
+# pww_mask.hip, pww_regions.hip and pww_canvas.hip restate fp32 formulas that must match a CPU restatement bit for bit: no FMA contraction.
+PER_FILE_FLAGS = {"pww_mask.hip": ["-ffp-contract=off"], "pww_regions.hip": ["-ffp-contract=off"], "pww_canvas.hip": ["-ffp-contract=off"]}
 
 
 def _newer(target, deps):
@@ -130,10 +139,11 @@ def build_experiments(force=False, verbose=False):
 
 
 def build_side(name, force=False, verbose=False):
-    """libpww_hip_<name>.so, one of SIDE_LIBS / SIDE_LIBS_CONV (include/pww_hip_<name>.h)."""
+    """libpww_hip_<name>.so, one of SIDE_LIBS / SIDE_LIBS_CONV / SIDE_LIBS_EXTRA (include/pww_hip_<name>.h)."""
     unit, headers, _ = ALL_SIDE_LIBS[name]
     lib = SIDE_PATHS[name]
-    deps = [os.path.join(CSRC, f) for f in [unit, "pww_common.h", "pww_side_host.h"] + headers] + [os.path.join(REPO, "include", h) for h in ("pww_hip.h", "pww_hip_%s.h" % name)] + [__file__]
+    public = ["pww_hip.h", "pww_hip_%s.h" % name] + SIDE_PUBLIC_HEADERS.get(name, [])
+    deps = [os.path.join(CSRC, f) for f in [unit, "pww_common.h", "pww_side_host.h"] + headers] + [os.path.join(REPO, "include", h) for h in public] + [__file__]
     if not force and not _newer(lib, deps):
         return lib
     return _build(lib, SIDE_UNITS[name], [], os.path.join(HERE, "build", name), verbose)
@@ -145,6 +155,7 @@ def build_linear(force=False, verbose=False): return build_side("linear", force,
 def build_regions(force=False, verbose=False): return build_side("regions", force, verbose)  # noqa: E704
 def build_lora(force=False, verbose=False): return build_side("lora", force, verbose)  # noqa: E704
 def build_convtail(force=False, verbose=False): return build_side("convtail", force, verbose)  # noqa: E704
+def build_canvas(force=False, verbose=False): return build_side("canvas", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):

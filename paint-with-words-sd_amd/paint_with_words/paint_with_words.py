@@ -25,7 +25,7 @@ from pww_hip.conditioning import check_prompt_chunks, prompt_chunk_count, check_
 from pww_hip.conditioning import check_region_prompts, check_loras, region_entries, encode_region_prompts
 from pww_hip.conditioning import (always_round, _extract_seed_and_sigma_from_context, _encode_text_color_inputs,  # noqa: F401
                                   _get_binary_mask, gaussian_blur_mask)
-from pww_hip.sampler import PwWSampler, initial_latents
+from pww_hip.sampler import PwWSampler, initial_latents, canvas_plan
 
 try:  # the reference's dependency; absent in the offline build image
     from diffusers import AutoencoderKL, LMSDiscreteScheduler, UNet2DConditionModel
@@ -152,6 +152,59 @@ def _batch_requests(n, color_contexts, negative_color_context, color_map_images,
     return [dict(c) for c in ctxs], [dict(c) if c else None for c in negs], maps, prompts, False, list(strip.values())
 
 
+CANVAS_MAX_WINDOW, CANVAS_MAX_WINDOWS, CANVAS_MAX_RAMP = 1024, 64, 64     # pixels; windows per canvas and ramp length (include/pww_hip_canvas.h)
+
+
+def _canvas_request(size, canvas_window, canvas_stride, canvas_ramp):
+    """The `canvas_window` / `canvas_stride` / `canvas_ramp` keywords of paint_with_words against the color map's (width, height) -> None
+    (the plain call: no window, or a canvas no larger than the window on both axes) or the sampler's canvas_plan in latent pixels."""
+    if canvas_window is None:
+        return None
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)      # noqa: E731
+    if not is_int(canvas_window) or canvas_window % 64 or not 64 <= canvas_window <= CANVAS_MAX_WINDOW:
+        raise ValueError("canvas_window must be a multiple of 64 pixels in 64 .. %d (got %r)" % (CANVAS_MAX_WINDOW, canvas_window))
+    stride = canvas_window // 2 if canvas_stride is None else canvas_stride
+    if not is_int(stride) or stride % 8 or not 8 <= stride <= canvas_window:
+        raise ValueError("canvas_stride must be a multiple of 8 pixels in 8 .. canvas_window = %d (got %r)" % (canvas_window, canvas_stride))
+    if not is_int(canvas_ramp) or not 0 <= canvas_ramp <= CANVAS_MAX_RAMP:
+        raise ValueError("canvas_ramp must be an integer number of latent pixels in 0 .. %d (got %r)" % (CANVAS_MAX_RAMP, canvas_ramp))
+    width, height = size
+    if width <= canvas_window and height <= canvas_window:
+        return None
+    if width % 8 or height % 8:
+        raise ValueError("canvas: the sides of a canvas larger than the window must be multiples of 8 pixels (the color map is %d x %d)" % (width, height))
+    if width < canvas_window or height < canvas_window:
+        raise ValueError("canvas: the %d x %d color map is smaller than the window of %d pixels on one axis" % (width, height, canvas_window))
+    plan = canvas_plan((height // 8, width // 8), canvas_window // 8, stride // 8, canvas_ramp)
+    if len(plan["ys"]) * len(plan["xs"]) > CANVAS_MAX_WINDOWS:
+        raise ValueError("canvas: %d x %d windows of %d pixels every %d pixels cover the %d x %d color map: more than %d (use a larger stride or window)"
+                         % (len(plan["ys"]), len(plan["xs"]), canvas_window, stride, width, height, CANVAS_MAX_WINDOWS))
+    return plan
+
+
+def _canvas_conditioning(encode, canvas, color_map, color_context, negative_color_context):
+    """The conditioning of a canvas request: every window is an image of its own whose color map is the crop of the canvas map under it.
+    encode(color map, color_context, negative_color_context) is _generate's call of _encode_text_color_inputs.
+    -> (conds, unconds, region tables: one per window in window order; the (extra_seeds, region_info) of the CANVAS for the initial latent).
+    The dicts are parsed once per window, so every window but the last parses a private copy with the seed / sigma tails still on; the last
+    parses the caller's own dicts, which lose their tails once, as in the plain call. Region seeds are read against the canvas map: a
+    context that carries one is parsed once more at canvas size for the initial latent (without one nothing is built at canvas size)."""
+    h, w = canvas["window"]
+    boxes = [(8 * x0, 8 * y0, 8 * (x0 + w), 8 * (y0 + h)) for y0 in canvas["ys"] for x0 in canvas["xs"]]
+    seeds_info = ({}, None)
+    if _extract_seed_and_sigma_from_context(dict(color_context))[1]:
+        extra_seeds, region_info, _, _ = encode(color_map, dict(color_context), None)
+        seeds_info = (extra_seeds, region_info)
+    conds, unconds, tables = [], [], []
+    for i, box in enumerate(boxes):
+        last = i == len(boxes) - 1
+        ctx = color_context if last else dict(color_context)
+        neg = negative_color_context if last or not negative_color_context else dict(negative_color_context)
+        _, region_info, cond, uncond = encode(color_map.crop(box), ctx, neg)
+        conds.append(cond), unconds.append(uncond), tables.append(region_info)
+    return conds, unconds, tables, seeds_info
+
+
 def _seeded_noise(tools, device, seeds, timesteps, seeds_info, sizes):
     """txt2img (:444-457): CPU-generated latents per seed exactly as :446, with the region seeds; `sizes`: (width, height) per request."""
     unet, scheduler = tools[1], tools[4]
@@ -183,7 +236,7 @@ def _txt2img_or_img2img(sizes, init_images, strength):
 def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
               unconditional_input_prompt, start, strength=None, map_sizes=None, on_step=None, use_region_sigma=True, shared=False,
               max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0, region_prompts=None, region_base_weight=0.0,
-              region_feather=0.0, loras=None):
+              region_feather=0.0, loras=None, canvas=None):
     """The body behind every face of the package (reference :414-506, paint_with_words_inpaint.py:160-262): conditioning per request (once
     if `shared`: every request has the same map, context and prompt), the timesteps, the initial state, one denoise loop over all images.
     Returns the final latents [n, 4, h, w].
@@ -193,7 +246,8 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
     function API, paint_with_words_inpaint.py:172). negative_color_contexts: None, or one dict (or None) per request like color_contexts --
     regions of the unconditional prompt (see paint_with_words). region_prompts: None, or one dict per request (_region_requests) -- a full
     prompt per colour, blended per latent pixel where guidance is combined (see paint_with_words). loras: None, or what check_loras made of the
-    `lora` / `region_loras` keywords."""
+    `lora` / `region_loras` keywords. canvas: None, or the plan of ONE request whose color map is larger than the UNet's window
+    (_canvas_request): the conditioning is formed per window on the crop of the map, the initial state at canvas size."""
     unet, text_encoder, tokenizer, scheduler = tools[1:]
     n = len(seeds)
     sampler = _sampler_for(unet, scheduler)   # also installs the attention plug
@@ -201,7 +255,14 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
     region_texts = [e[1] for r in (region_prompts or []) for e in region_entries(r)]
     min_chunks = _batch_prompt_chunks(tokenizer, (prompts[:1] if shared else prompts) + [unconditional_input_prompt] + region_texts, max_prompt_chunks)
     negs, any_neg = _negative_contexts(negative_color_contexts, n, color_map_images)
-    for i in range(1 if shared else n):
+    if canvas is not None:
+        encode = lambda color_map, ctx, neg: _encode_text_color_inputs(      # noqa: E731
+            text_encoder, tokenizer, device, color_map, ctx, prompts[0], unconditional_input_prompt, dtype=_unet_dtype(unet), use_sigma=use_region_sigma,
+            max_prompt_chunks=max_prompt_chunks, min_prompt_chunks=min_chunks, negative_color_context=neg, negative_maps=any_neg)
+        conds, unconds, tables, canvas_seeds = _canvas_conditioning(encode, canvas, color_map_images[0], color_contexts[0], negs[0])
+        n_w, shared = len(conds), False
+        seeds_info = [canvas_seeds]
+    for i in range(0 if canvas is not None else 1 if shared else n):
         color_map = color_map_images[i]
         if map_sizes is not None and color_map is not None:
             color_map = color_map.resize(map_sizes[i], Image.NEAREST)
@@ -211,7 +272,11 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
             negative_color_context=negs[i], negative_maps=any_neg)
         conds.append(cond), unconds.append(uncond), seeds_info.append((extra_seeds, region_info))
     regions = None
-    if region_prompts:
+    if region_prompts and canvas is not None:
+        # one plan per window: the region masks (and their feather) are formed on the window's crop of the color map
+        regions = [encode_region_prompts(text_encoder, tokenizer, device, table[1], region_prompts[0], guidance_scale, uncond, dtype=_unet_dtype(unet),
+                                         region_base_weight=region_base_weight, region_feather=region_feather) for table, uncond in zip(tables, unconds)]
+    elif region_prompts:
         # one plan per request (one for all when the requests share everything): K more rows of the same UNet evaluation
         one = shared and all(r is region_prompts[0] for r in region_prompts)
         regions = [encode_region_prompts(text_encoder, tokenizer, device, seeds_info[0 if shared else i][1][1], region_prompts[i], guidance_scale,
@@ -229,9 +294,13 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
 
     latents, extra_channels = start(tools, device, seeds, timesteps, seeds_info)
     more = {} if regions is None else {"regions": regions}        # (a call without region prompts is, argument for argument, the call of before)
+    if canvas is not None:
+        more["canvas"] = canvas
     if loras is not None:
+        rows = n if canvas is None else n_w         # (the rows of a canvas request are its windows: the one request's adapters for each of them)
         colors = [[e[0] for e in region_entries(r)] for r in region_prompts] if region_prompts else [[]] * n
-        more["lora_rows"] = pww_hip.lora.row_plan(n, colors, loras[0], loras[1], pww_hip.lora.state_of(unet).index)
+        region_loras = loras[1] if canvas is None or loras[1] is None else list(loras[1]) * n_w
+        more["lora_rows"] = pww_hip.lora.row_plan(rows, colors if canvas is None else colors * n_w, loras[0], region_loras, pww_hip.lora.state_of(unet).index)
     with pww_hip.miopen_find():
         return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra_channels,
                               on_step=on_step, negative_strength=negative_strength, **more)
@@ -272,6 +341,9 @@ def paint_with_words(
     negative_strength: float = 1.0,
     lora=None,
     region_loras=None,
+    canvas_window: Optional[int] = None,
+    canvas_stride: Optional[int] = None,
+    canvas_ramp: int = 0,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -297,19 +369,32 @@ def paint_with_words(
     `lora` / `region_loras` (extension): LoRA adapters loaded with pww_hip.lora.load_lora(unet, source, name) on the UNet of
     `preloaded_utils`, applied unmerged and per row of the UNet evaluation: lora = "name" or ("name", scale) is the adapter of the prompt's
     row, the unconditional row and every region without an adapter of its own (alone it behaves like merged weights); region_loras =
-    {(r, g, b) | "#rrggbb": "name" | ("name", scale)} gives a colour of region_prompts its own adapter."""
+    {(r, g, b) | "#rrggbb": "name" | ("name", scale)} gives a colour of region_prompts its own adapter.
+    `canvas_window` / `canvas_stride` / `canvas_ramp` (extension): a color map larger than `canvas_window` pixels (a multiple of 64, at most
+    1024; square windows) is denoised as overlapping windows of that size, one every `canvas_stride` pixels (a multiple of 8 in 8 ..
+    canvas_window; None: half the window) with the last window of an axis clamped to the canvas's end, at most 64 windows (MultiDiffusion,
+    Bar-Tal et al. 2023): per step the windows are the images of ONE UNet evaluation and the mean of their noise predictions per latent pixel
+    -- weighted, with canvas_ramp > 0 (latent pixels, at most 64), by a linear ramp min(distance to the window's edge + 1, canvas_ramp) along
+    each axis -- takes one scheduler step on the canvas. A window is an image of its own for conditioning: its color map is the crop of the
+    canvas map under it, and blur sigmas, negative regions, region masks and their feather are formed on the crop; a colour that is absent
+    from a window gives zero maps there. The score statistic a weight_function reads (qk.max() ...) is per window, because it is per image.
+    The initial latent (with region seeds, against the whole map) and the img2img encoding are formed at canvas size. None (the default), or
+    a map no larger than the window on both axes, is the plain call; a map smaller than the window on one axis, a side that is not a
+    multiple of 8, more than 64 windows or a value out of range raise ValueError. record_attention_maps() is refused around such a call.
+    Not part of this: the *_batch forms, the inpaint function, both pipeline classes, windows spread over several GPUs, non-square windows."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context)
     loras = check_loras(lora, region_loras, region_prompts, tools=preloaded_utils)
     color_map_image.size     # the reference dereferences it unconditionally (:414): None raises here too
+    canvas = _canvas_request(color_map_image.size, canvas_window, canvas_stride, canvas_ramp)
     tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
     start, strength = _txt2img_or_img2img([color_map_image.size], None if init_image is None else [init_image], strength)
     latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps, guidance_scale,
                         weight_function, unconditional_input_prompt, start, strength, shared=True, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=[negative_color_context], negative_strength=negative_strength,
                         region_prompts=_region_requests(region_prompts, 1), region_base_weight=region_base_weight, region_feather=region_feather,
-                        loras=loras)
+                        loras=loras, **({} if canvas is None else {"canvas": canvas}))
     out = _finish(tools, latents, return_latents)
     return out if return_latents else out[0]
 

@@ -26,6 +26,9 @@ LORA_LIB_PATH = os.environ.get("PWW_HIP_LORA_LIB", os.path.join(_HERE, "libpww_h
 #   convtail  conv2 of a ResnetBlock2D with the block's 1 x 1 shortcut as further K-slabs (include/pww_hip_convtail.h): ops.conv3x3_shortcut.
 #             Its spec is in SIDE_CONV below.
 CONVTAIL_LIB_PATH = os.environ.get("PWW_HIP_CONVTAIL_LIB", os.path.join(_HERE, "libpww_hip_convtail.so"))
+#   canvas    canvases larger than the UNet's window: the gather of the windows and the combine of their noise predictions
+#             (include/pww_hip_canvas.h): ops.canvas_gather, ops.canvas_combine. Its spec is in SIDE_EXTRA below.
+CANVAS_LIB_PATH = os.environ.get("PWW_HIP_CANVAS_LIB", os.path.join(_HERE, "libpww_hip_canvas.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -82,6 +85,12 @@ LORA_MAX_ADAPTERS, LORA_MAX_RANK, LORA_MAX_SEGMENTS = 8, 128, 3      # PWW_LORA_
 # every symbol include/pww_hip_convtail.h declares for libpww_hip_convtail.so
 CONVTAIL_EXPORTS = ("pww_convtail_version", "pww_convtail_last_error", "pww_convtail_workspace_bytes", "pww_convtail_fwd")
 CONVTAIL_MIN_VERSION = 100
+
+
+# every symbol include/pww_hip_canvas.h declares for libpww_hip_canvas.so
+CANVAS_EXPORTS = ("pww_canvas_version", "pww_canvas_last_error", "pww_canvas_gather", "pww_canvas_combine")
+CANVAS_MIN_VERSION = 100
+CANVAS_MAX_WINDOWS, CANVAS_MAX_RAMP, CANVAS_MIN_WINDOW, CANVAS_MAX_WINDOW = 64, 64, 8, 128      # PWW_CANVAS_* of the header
 
 
 class AttnDesc(ctypes.Structure):
@@ -337,16 +346,25 @@ SIDE_CONV = {
         "pww_convtail_workspace_bytes": ([_P(ConvTailDesc)], _sz),
         "pww_convtail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(ConvTailDesc), _vp, _sz, _vp], _int)}),
 }
+# the open-ended table (build.py: SIDE_LIBS_EXTRA): SIDE, SIDE_MORE and SIDE_CONV are closed, and every later side library is a row here
+SIDE_EXTRA = {
+    "canvas": dict(path="CANVAS_LIB_PATH", exports=CANVAS_EXPORTS, min_version=CANVAS_MIN_VERSION, missing_ok=False, needs="canvases larger than the window need it", sigs={
+        "pww_canvas_gather": ([_vp, _vp, _P(_i32), _i32, _P(_i32), _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp], _int),
+        "pww_canvas_combine": ([_vp, _vp, _vp, _vp, _f32, _vp, _P(_i32), _i32, _P(_i32), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp], _int)}),
+}
 _side = {}      # name -> loaded handle
 
 
 def side_spec(name):
-    """The table entry of a side library (SIDE, SIDE_MORE or SIDE_CONV)."""
-    return SIDE[name] if name in SIDE else SIDE_MORE[name] if name in SIDE_MORE else SIDE_CONV[name]
+    """The table entry of a side library (SIDE, SIDE_MORE, SIDE_CONV or SIDE_EXTRA)."""
+    for table in (SIDE, SIDE_MORE, SIDE_CONV):
+        if name in table:
+            return table[name]
+    return SIDE_EXTRA[name]
 
 
 def load_side(name):
-    """libpww_hip_<name>.so of SIDE / SIDE_MORE / SIDE_CONV, loaded once. A missing file returns None where the table says so (scope: the caller keeps the
+    """libpww_hip_<name>.so of SIDE / SIDE_MORE / SIDE_CONV / SIDE_EXTRA, loaded once. A missing file returns None where the table says so (scope: the caller keeps the
     materialised route) and raises otherwise -- there is no second implementation to fall back to. A file that is there but stale, broken
     or short of an entry point raises. Every failure is a PwwHipError with the rebuild hint."""
     lib = _side.get(name)
@@ -407,6 +425,11 @@ def load_lora():
 def load_convtail():
     lib = _side.get("convtail")
     return lib if lib is not None else load_side("convtail")
+
+
+def load_canvas():
+    lib = _side.get("canvas")
+    return lib if lib is not None else load_side("canvas")
 
 
 class experiments:

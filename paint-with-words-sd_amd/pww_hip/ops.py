@@ -904,6 +904,79 @@ def region_combine(eps, masks, weights, scales, guidance_scale):
     return out
 
 
+# ---- canvases larger than the UNet's window (libpww_hip_canvas.so, include/pww_hip_canvas.h) ---------------------------------------------
+def canvas_windows(L, win, stride):
+    """The window origins along an axis of latent length L: 0, stride, 2 stride, ... below L - win, then L - win (the last window is
+    clamped to the end: its origin may be odd and its overlap larger). A tuple of ints."""
+    L, win, stride = int(L), int(win), int(stride)
+    if win < 1 or L < win or not 1 <= stride <= win:
+        raise ValueError("canvas_windows: length %d, window %d, stride %d (1 <= stride <= window <= length)" % (L, win, stride))
+    return tuple(range(0, L - win, stride)) + (L - win,)
+
+
+def _canvas_origins(ys, xs):
+    ys, xs = [int(v) for v in ys], [int(v) for v in xs]
+    if not ys or not xs:
+        raise PwwHipError("canvas: the window origins ys and xs must not be empty")
+    return ys, xs, (ctypes.c_int32 * len(ys))(*ys), (ctypes.c_int32 * len(xs))(*xs)
+
+
+def canvas_gather(canvas, ys, xs, h, w, denom, copies, dtype):
+    """The windows of a canvas latent as UNet input rows: canvas fp32 [C, Hc, Wc] (or [1, C, Hc, Wc]) -> `dtype` [copies * ny * nx, C, h, w],
+    window iy * nx + ix = canvas[:, ys[iy]:ys[iy] + h, xs[ix]:xs[ix] + w] / denom (one fp32 division, one rounding), the whole set
+    repeated `copies` times (the row classes of a folded call). One launch."""
+    _require_gpu(canvas)
+    if canvas.dim() == 4 and canvas.shape[0] == 1:
+        canvas = canvas[0]
+    if canvas.dtype != torch.float32 or canvas.dim() != 3:
+        raise PwwHipError("canvas_gather needs a float32 canvas [C, Hc, Wc] (or [1, C, Hc, Wc])")
+    if dtype not in _DT:
+        raise PwwHipError("canvas_gather: the output type must be float16 or bfloat16 (got %s)" % dtype)
+    ys, xs, ys_c, xs_c = _canvas_origins(ys, xs)
+    canvas = canvas.contiguous()
+    C, Hc, Wc = (int(v) for v in canvas.shape)
+    out = torch.empty((int(copies) * len(ys) * len(xs), C, int(h), int(w)), dtype=dtype, device=canvas.device)
+    lib = _lib.load_canvas()
+    with torch.cuda.device(canvas.device):
+        _lib.check(lib.pww_canvas_gather(_ptr(canvas), _ptr(out), ys_c, len(ys), xs_c, len(xs), C, Hc, Wc, int(h), int(w), float(denom), int(copies),
+                                         _DT[dtype], _stream()), "pww_canvas_gather", lib)
+    return out
+
+
+def canvas_combine(eps, ys, xs, canvas_hw, guidance_scale, ramp=0, masks=None, weights=None, scales=None):
+    """The canvas-sized noise prediction of one step (returns fp32 [1, C, Hc, Wc]): eps [(K + 2) n_w, C, h, w] float16 / bfloat16 with rows
+    [base x n_w, region 1 x n_w, ..., region K x n_w, unconditional x n_w] for the n_w = ny nx windows at (ys[iy], xs[ix]); per canvas pixel
+    the mean of the covering windows' guided predictions, weighted by p = r_h(ly) r_w(lx), r_L(l) = min(min(l, L - 1 - l) + 1, ramp) (1 when
+    ramp = 0), in ascending window index. Without region prompts (masks None, K = 0) a window's prediction is e_u + g (e_0 - e_u); with them
+    -- masks fp32 [n_w, K, h, w], weights / scales fp32 [n_w, K], one set per window -- it is region_combine's expression. One launch."""
+    _require_gpu(eps, masks, weights, scales)
+    ys, xs, ys_c, xs_c = _canvas_origins(ys, xs)
+    n_w = len(ys) * len(xs)
+    if eps.dtype not in _DT or eps.dim() != 4:
+        raise PwwHipError("canvas_combine needs a float16 / bfloat16 [(K + 2) n_w, C, h, w] tensor")
+    K = 0
+    if masks is not None or weights is not None or scales is not None:
+        if masks is None or weights is None or scales is None or masks.dim() != 4:
+            raise PwwHipError("canvas_combine: region prompts need masks fp32 [n_w, K, h, w] with weights and scales fp32 [n_w, K]")
+        K = int(masks.shape[1])
+        if (int(masks.shape[0]) != n_w or tuple(eps.shape[-2:]) != tuple(masks.shape[-2:]) or tuple(weights.shape) != (n_w, K) or tuple(scales.shape) != (n_w, K)
+                or any(t.dtype != torch.float32 for t in (masks, weights, scales))):
+            raise PwwHipError("canvas_combine: eps %s of %d windows does not go with masks %s, weights %s and scales %s (fp32)"
+                              % (tuple(eps.shape), n_w, tuple(masks.shape), tuple(weights.shape), tuple(scales.shape)))
+        masks, weights, scales = masks.contiguous(), weights.contiguous(), scales.contiguous()
+    if eps.shape[0] != (K + 2) * n_w:
+        raise PwwHipError("canvas_combine: eps has %d rows for %d windows and %d regions ((K + 2) n_w = %d)" % (eps.shape[0], n_w, K, (K + 2) * n_w))
+    eps = eps.contiguous()
+    C, h, w = (int(v) for v in eps.shape[1:])
+    Hc, Wc = (int(v) for v in canvas_hw)
+    out = torch.empty((1, C, Hc, Wc), dtype=torch.float32, device=eps.device)
+    lib = _lib.load_canvas()
+    with torch.cuda.device(eps.device):
+        _lib.check(lib.pww_canvas_combine(_ptr(eps), _ptr(masks), _ptr(weights), _ptr(scales), float(guidance_scale), _ptr(out), ys_c, len(ys), xs_c,
+                                          len(xs), K, C, Hc, Wc, h, w, int(ramp), _DT[eps.dtype], _stream()), "pww_canvas_combine", lib)
+    return out
+
+
 # ---- GroupNorm (+ per-(image, channel) addend, + SiLU) of the blocks that call the attention path ------------------------------------
 def group_norm(x, num_groups, weight=None, bias=None, eps=1e-5, add=None, act=None, workspace=None, out=None, pre_bias=None):
     """act(GroupNorm(x + add[:, :, None, None])) for a [B, C, H, W] float16 / bfloat16 tensor in NCHW-contiguous or channels_last memory

@@ -19,6 +19,10 @@ LoRA adapters (pww_hip/lora.py) are chosen per row by two device arrays of the U
 Region prompts (a full prompt per colour, `regions=`) add K rows per image in each of the three: K more batch-1 calls in "eager", rows
 [base x n, region 1 x n, ..., region K x n, uncond x n] in "folded" / "graph" (_fold_regions), and the per-pixel blend of
 ops.region_combine where classifier-free guidance is combined otherwise.
+A canvas larger than the UNet's window (`canvas=`, MultiDiffusion) is denoised as overlapping windows: the windows are the images of the UNet
+evaluation -- one context dict, one region plan, one LoRA row per window -- around two launches per step: ops.canvas_gather forms the windows'
+rows from the fp32 canvas latent, ops.canvas_combine the canvas-sized noise prediction from the UNet's output, and one scheduler.step follows
+on the canvas.
 """
 import torch
 
@@ -53,6 +57,15 @@ def initial_latents(seed, in_channels, height, width, region_masks=None, extra_s
             latents[:, :, foreground] = summed[:, :, foreground]
         out.append(latents)
     return torch.cat(out, dim=0)
+
+
+def canvas_plan(canvas_hw, window, stride, ramp=0):
+    """The plan `PwWSampler.sample(canvas=)` takes, in latent pixels: canvas_hw = (Hc, Wc), a square window of `window`, origins every
+    `stride` with the last window clamped to the end (ops.canvas_windows), `ramp` the length of the linear weight ramp at a window's edges
+    (0: every covering window counts the same). Window iy * nx + ix has its origin at (ys[iy], xs[ix])."""
+    Hc, Wc = (int(v) for v in canvas_hw)
+    return {"size": (Hc, Wc), "window": (int(window), int(window)), "ys": ops.canvas_windows(Hc, window, stride),
+            "xs": ops.canvas_windows(Wc, window, stride), "ramp": int(ramp)}
 
 
 def _as_list(x, n):
@@ -371,15 +384,16 @@ class PwWSampler:
         self.handoff_pending = False     # the last request issued launches with an in-kernel hand-off (PWW_QPROJ_STAT=0 / shapes the
                                          # to_q GEMM does not cover): its latents must not reach a caller before check_errors() has looked
 
-    def _static_context(self, folded, weight_function, latents, timesteps, rec=None):
+    def _static_context(self, folded, weight_function, latents, timesteps, rec=None, batch_shape=None):
         """Captured graphs read the context tensors by ADDRESS: keep one set of static tensors alive and copy each new
         request's values into them; rebuild the graphs when the geometry changes. The weight function and the schedule are
         NOT part of the key while the function's scalars travel in device words (CoeffSlots) -- fresh lambdas, other
         constants, another step count all replay the same graph; only the per-step fall-back keys them."""
         def tensor_sig(d):      # (the full-resolution fallback map is not part of the geometry: it exists only once a layer asked for it)
             return tuple(sorted((k, tuple(v.shape), v.dtype) for k, v in d.items() if torch.is_tensor(v) and k != ORIG))
+        # (a canvas request is keyed on its window batch [n_w, C, h, w] -- what the UNet sees -- not on the canvas or the origins)
         # (recording attention maps on / off, per layer or not, is geometry too: the captured graph holds the probabilities launches or it does not)
-        sig = (tuple(latents.shape), tensor_sig(folded), tuple(sorted((k, v) for k, v in folded.items() if isinstance(v, int) and not isinstance(v, bool))),
+        sig = (tuple(latents.shape) if batch_shape is None else tuple(batch_shape), tensor_sig(folded), tuple(sorted((k, v) for k, v in folded.items() if isinstance(v, int) and not isinstance(v, bool))),
                None if rec is None else ("attention maps", rec.per_layer))
         if self._lora is not None:      # LoRA launches are part of the graph: with which padded rank, over which stacks -- not for which rows
             sig = sig + (self._lora.signature(),)
@@ -414,6 +428,34 @@ class PwWSampler:
                 self._fallback_sig = fsig
         return self._static_folded
 
+    def _input_scale(self, t, sigma):
+        """What scheduler.scale_model_input divides by at timestep t, as one fp32 number (the canvas path divides inside the gather launch):
+        1 for a scheduler that hands its input back, sqrt(sigma^2 + 1) formed in fp32 like the LMS scheduler forms it. The scheduler is asked
+        with a one-element probe, so one that scales in another way is refused instead of mis-scaled."""
+        where = sigma.device if torch.is_tensor(sigma) else "cpu"
+        probe = float(self.scheduler.scale_model_input(torch.ones(1, dtype=torch.float32, device=where), t).reshape(-1)[0])
+        if probe == 1.0:
+            return 1.0
+        denom = float((torch.as_tensor(sigma, dtype=torch.float32).cpu() ** 2 + 1) ** 0.5)
+        if abs(probe * denom - 1.0) > 1e-5:
+            raise ValueError("canvas: the scheduler scales its input by %g at t = %s, which is neither 1 nor 1 / sqrt(sigma^2 + 1) = %g" % (probe, float(t), 1.0 / denom))
+        return denom
+
+    def _canvas_check(self, canvas, latents, extra_channels):
+        """The plan of a canvas request against its latent -> (n_w, (h, w)). The origins themselves are checked by the library."""
+        if extra_channels is not None:
+            raise ValueError("canvas: extra UNet input channels (inpainting) are not supported")
+        if attnmaps.active() is not None:
+            raise ValueError("canvas: record_attention_maps() is not supported with a canvas larger than the window (stitched maps are not built)")
+        if latents.dim() != 4 or latents.shape[0] != 1 or latents.dtype != torch.float32:
+            raise ValueError("canvas: the latent must be one float32 canvas [1, C, Hc, Wc] (got %s %s)" % (tuple(latents.shape), latents.dtype))
+        if tuple(canvas["size"]) != tuple(latents.shape[-2:]):
+            raise ValueError("canvas: the plan is for a %s latent but the latent is %s" % (tuple(canvas["size"]), tuple(latents.shape[-2:])))
+        udt = self.unet.dtype if hasattr(self.unet, "dtype") else next(self.unet.parameters()).dtype
+        if udt not in (torch.float16, torch.bfloat16):
+            raise ValueError("canvas: the UNet must run in float16 or bfloat16 (got %s)" % udt)
+        return len(canvas["ys"]) * len(canvas["xs"]), tuple(canvas["window"])
+
     def _sigma_and_index(self, i, t):
         sch = self.scheduler
         ts = sch.timesteps
@@ -425,18 +467,25 @@ class PwWSampler:
 
     @torch.no_grad()
     def sample(self, cond, uncond, latents, timesteps, guidance_scale, weight_function, extra_channels=None,
-               on_step=None, negative_strength=1.0, regions=None, lora_rows=None):
+               on_step=None, negative_strength=1.0, regions=None, lora_rows=None, canvas=None):
         """cond / uncond: the two context dicts of the PwW protocol, or one dict per image (per-image prompts / maps).
         regions: None, or the region prompts of the request -- one plan of conditioning.encode_region_prompts or one per image: K more rows
         per image, blended per latent pixel (ops.region_combine) where guidance is combined otherwise.
         An unconditional dict that carries weight maps (negative regions) is evaluated with `negative_strength * weight_function`.
         lora_rows: None (no row has an adapter), or lora.row_plan's (adapters, scales) for the rows [base x n, region 1 x n, ..., uncond x n].
         latents: [n_images, C, h, w] already scaled by init_noise_sigma (or noised for img2img).
+        canvas: None, or a canvas_plan(): `latents` is then ONE float32 canvas [1, C, Hc, Wc] denoised as n_w = ny nx overlapping windows --
+        cond / uncond / regions are one per window (or one for all), lora_rows is planned with n = n_w, and every step gathers the windows
+        (ops.canvas_gather), evaluates the UNet on (K + 2) n_w rows and combines them into the canvas's noise prediction (ops.canvas_combine)
+        for one scheduler.step on the canvas. A weight_function's score statistic (qk.max() ...) is per window, as it is per image. Raises
+        ValueError while record_attention_maps() is active, and with extra_channels.
         extra_channels: inpaint's cat([mask, masked_image_latents]) ([n or 1, 5, h, w]) or None."""
         sch, unet, dev = self.scheduler, self.unet, latents.device
         self._errors.poll(wait=False)      # a hand-off time-out of an earlier request surfaces here (or in check_errors())
         install(unet)      # the plug is a class-level patch (:193-195): put it back if somebody removed it since __init__
-        n = latents.shape[0]
+        n, frame = latents.shape[0], tuple(latents.shape[-2:])      # images of the UNet evaluation and their latent size
+        if canvas is not None:
+            n, frame = self._canvas_check(canvas, latents, extra_channels)
         udt = unet.dtype if hasattr(unet, "dtype") else next(unet.parameters()).dtype
         conds, unconds = _as_list(cond, n), _as_list(uncond, n)
         blend = None
@@ -444,9 +493,9 @@ class PwWSampler:
             if any(_has_negative_maps(u) for u in unconds):
                 raise ValueError("region prompts do not combine with negative regions")
             plans = _as_list(regions, n)
-            if any(tuple(p["masks"].shape[-2:]) != tuple(latents.shape[-2:]) for p in plans):
+            if any(tuple(p["masks"].shape[-2:]) != frame for p in plans):
                 raise ValueError("region prompts: the color map gives %s region masks but the latent is %s: the color map must be 8 x the latent's size"
-                                 % (sorted({tuple(p["masks"].shape[-2:]) for p in plans}), tuple(latents.shape[-2:])))
+                                 % (sorted({tuple(p["masks"].shape[-2:]) for p in plans}), frame))
             stack = lambda key: torch.stack([p[key] for p in plans], dim=0).to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
             blend = {"plans": plans, "K": len(plans[0]["contexts"]), "masks": stack("masks"), "weights": stack("weights"), "scales": stack("scales")}
         self._lora = _lora.state_of(unet)
@@ -472,9 +521,14 @@ class PwWSampler:
         if self.mode != "eager":
             folded = _fold_context(cond, uncond, n, dev, negative_strength) if blend is None else _fold_regions(cond, regions, uncond, n, dev)
             if self._graphed is not None:
-                folded = self._static_context(folded, weight_function, latents, timesteps, rec)
+                if canvas is None:
+                    folded = self._static_context(folded, weight_function, latents, timesteps, rec)
+                else:
+                    folded = self._static_context(folded, weight_function, latents, timesteps, rec, batch_shape=(n, latents.shape[1]) + frame)
         if extra_channels is not None and extra_channels.shape[0] != n:
             extra_channels = extra_channels.expand(n, -1, -1, -1)
+        if canvas is not None:
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, None, on_step, None, negative_strength, blend, canvas)
         if rec is None:
             return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, None, negative_strength, blend)
         static = self._static_maps if self._graphed is not None else None
@@ -489,9 +543,11 @@ class PwWSampler:
                 d.pop(ATTN_RECORDER, None)
             rec.end_request(static=static is not None)
 
-    def _denoise(self, conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength=1.0, blend=None):
-        """The loop of sample() (reference :470-506). blend: the region prompts of the request (sample()), or None."""
-        sch, unet, n = self.scheduler, self.unet, latents.shape[0]
+    def _denoise(self, conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength=1.0, blend=None,
+                 canvas=None):
+        """The loop of sample() (reference :470-506). blend: the region prompts of the request (sample()), or None. canvas: the plan of a
+        canvas request, or None -- `latents` is then the canvas, and the n images of the UNet evaluation are its windows."""
+        sch, unet, n = self.scheduler, self.unet, latents.shape[0] if canvas is None else len(conds)
         udt = unet.dtype if hasattr(unet, "dtype") else next(unet.parameters()).dtype
         zero_function = lambda w, sigma, qk: 0.0      # noqa: E731  (the reference's unconditional pass, :493)
         ns = float(negative_strength)
@@ -502,7 +558,13 @@ class PwWSampler:
         calls = self._lora_calls        # eager mode with LoRA adapters loaded: every batch-1 call has its own one-row assignment
         for i, t in enumerate(timesteps):
             sigma, _ = self._sigma_and_index(i, t)
-            x = sch.scale_model_input(latents, t)
+            if canvas is None:
+                x = sch.scale_model_input(latents, t)
+            else:
+                # the windows' rows, scaled and rounded to the UNet's type by one launch: [n_w, C, h, w] for the batch-1 calls of "eager",
+                # the K + 2 row classes of the folded call otherwise; outside the captured graph in hipGraph mode
+                x = ops.canvas_gather(latents, canvas["ys"], canvas["xs"], canvas["window"][0], canvas["window"][1], self._input_scale(t, sigma),
+                                      1 if self.mode == "eager" else K + 2, udt)
             if extra_channels is not None:
                 x = torch.cat([x, extra_channels.to(x.dtype)], dim=1)
             if self.mode == "eager":
@@ -525,10 +587,10 @@ class PwWSampler:
                         self._lora_call(calls[(K + 1) * n + j], unconds[j], n)
                     eps_u.append(unet(x[j:j + 1], t, encoder_hidden_states=unconds[j]).sample)
                 eps_c, eps_u = torch.cat(eps_c), torch.cat(eps_u)
-                out = torch.cat([eps_c] + [torch.cat(r) for r in eps_r] + [eps_u]) if K else None
+                out = torch.cat([eps_c] + [torch.cat(r) for r in eps_r] + [eps_u]) if K or canvas is not None else None
             else:
                 folded.update({"SIGMA": sigma, "WEIGHT_FUNCTION": weight_function})
-                x2 = torch.cat([x] * (K + 2), dim=0).to(udt)
+                x2 = torch.cat([x] * (K + 2), dim=0).to(udt) if canvas is None else x
                 if self.mode == "graph":
                     slots = folded[COEFF_SLOTS]
                     if not slots.unsupported and not slots.update(weight_function, sigma):
@@ -539,7 +601,11 @@ class PwWSampler:
                 else:
                     out = unet(x2, t, encoder_hidden_states=folded).sample
                 eps_c, eps_u = out[:n], out[n:]
-            if K:
+            if canvas is not None:
+                # rows [base x n_w, region 1 x n_w, ..., uncond x n_w] -> the canvas's fp32 [1, C, Hc, Wc], one launch (outside the graph too)
+                more = {} if not K else {"masks": blend["masks"], "weights": blend["weights"], "scales": blend["scales"]}
+                noise_pred = ops.canvas_combine(out, canvas["ys"], canvas["xs"], canvas["size"], guidance_scale, canvas["ramp"], **more)
+            elif K:
                 # rows [base x n, region 1 x n, ..., uncond x n] -> fp32 [n, C, h, w], one launch; outside the captured graph in hipGraph mode
                 combine = ops.region_combine if out.dtype in (torch.float16, torch.bfloat16) else region_blend_fp32
                 noise_pred = combine(out, blend["masks"], blend["weights"], blend["scales"], guidance_scale)
