@@ -10,6 +10,7 @@ head split / merge disappears into kernel strides, and scores + bias + softmax +
 HIP kernel. The user's ``weight_function(w, sigma, qk)`` still receives ``qk`` -- as a ``QKProxy``
 whose reductions are computed by the score-reduction kernel instead of from a materialised tensor.
 """
+import collections
 import math
 import os
 import warnings
@@ -634,12 +635,13 @@ def _fused_weight(attn, names, dtype=None):
     mods = [getattr(attn, n) for n in names]
     if any(getattr(m, "bias", None) is not None for m in mods):
         return None
-    dtype = dtype or mods[0].weight.dtype
-    key = tuple((m.weight.data_ptr(), m.weight._version, m.weight.dtype, m.weight.device) for m in mods) + (dtype,)
+    ws = [m.weight for m in mods]
+    dtype = dtype or ws[0].dtype
+    key = tuple([(w.data_ptr(), w._version, w.dtype, w.device) for w in ws]) + (dtype,)
     cache = attn.__dict__.setdefault("_pww_fused", {})
     ent = cache.get(names)
     if ent is None or ent[0] != key:
-        ent = (key, torch.cat([m.weight.detach().to(dtype) for m in mods], dim=0).contiguous())
+        ent = (key, torch.cat([w.detach().to(dtype) for w in ws], dim=0).contiguous())
         cache[names] = ent
     return ent[1]
 
@@ -684,46 +686,68 @@ def _attention_and_out(attn, hidden_states, context):
 def _attention(attn, hidden_states, context, out_linear):
     """-> (tensor, projected): with `out_linear` (the layer's to_out[0]) and a layer pww_cross_attn_fwd_parts_out covers, the
     projection is applied inside the attention launch and `projected` is True."""
-    is_dict = True
-    if context is not None:
-        if isinstance(context, dict) or hasattr(context, "keys"):
-            context_tensor = context["CONTEXT_TENSOR"]
-        else:               # plain tensor context: vanilla pipelines keep working (the reference's try/except, :65-69)
-            context_tensor = context
-            is_dict = False
-    else:
+    p = _project(attn, hidden_states, context)
+    return _launch(attn, p, _plan(attn, p, out_linear), out_linear)
+
+
+# What _project hands on. query: in the compute dtype `cdt` like key / value, or still deferred (a _LazyQuery: see _query); ctx: a PwW dict or None
+_Proj = collections.namedtuple("_Proj", "hidden query key value cdt pdt lo ctx")
+# What one attention call launches, decided once by _plan. family: "none" (nothing softmax can see: a number, a 0-dim tensor, a bare
+# statistic), "scoped" (c * w * a per-head / per-row statistic on libpww_hip_scope.so; scoped = (kind, scope, scalar)), "symbolic" (c * w
+# [* stat(qk)]: the map, stat = (statistics [B, 4] | None, STAT_* kind, Python scalar) and what the statistic's launch needs), "vector" (the
+# map with a per-row coefficient vector) or "materialised" (a tensor). bias_coeff: fp32 [B], the row gate or the vector family's coefficient.
+_Plan = collections.namedtuple("_Plan", "family query bias bias_coeff stat parts scratch coeff_dev bias_cols compact gated scoped",
+                               defaults=(None, None, None, None, None, None, 0, None, 0, None))
+
+
+def _query(p):
+    """The query of a projection in the compute dtype; a deferred to_q runs here. Every plan asks once."""
+    q = p.query
+    return _half(q.get(), p.cdt) if isinstance(q, _LazyQuery) else q
+
+
+def _qk_shape(attn, p):
+    return (p.hidden.shape[0] * attn.heads, p.hidden.shape[1], p.key.shape[1])
+
+
+def _project(attn, hidden_states, context):
+    """Step 1 of _attention: context parsing, dtype alignment and one of three projection strategies, each followed by the layer's LoRA update --
+    q|k|v in one GEMM (self-attention), k|v in one GEMM with the query deferred (cross-attention), or the module's own three."""
+    ctx = None
+    if context is None:
         context_tensor = hidden_states
+    elif isinstance(context, dict) or hasattr(context, "keys"):
+        context_tensor, ctx = context["CONTEXT_TENSOR"], context
+    else:                   # plain tensor context: vanilla pipelines keep working (the reference's try/except, :65-69)
+        context_tensor = context
     if not hidden_states.is_cuda:
         raise PwwHipError("pww_hip attention needs HIP tensors (got %s); the CPU restatement lives in oracle/ "
                           "and is test-only" % hidden_states.device)
-
-    wdt = attn.to_q.weight.dtype
+    wq = attn.to_q.weight
+    wdt, C = wq.dtype, wq.shape[0]
     if context_tensor.dtype != wdt and not torch.is_autocast_enabled():
         context_tensor = context_tensor.to(wdt)   # text encoder is fp32 in the reference (:171)
     if hidden_states.dtype != wdt and not torch.is_autocast_enabled():
         hidden_states = hidden_states.to(wdt)
-    C = attn.to_q.weight.shape[0]
-    query = lazy_q = None
-    # Fused projections in the dtype the reference's path computes in: under torch.autocast("cuda") (how the reference runs,
-    # :60 / :392: fp16 UNet or not, fp32 text encoder :171) that is the autocast dtype, and the concatenated weights are kept
-    # in it, so autocast has nothing left to cast per call.
+    # Fused projections in the dtype the reference's path computes in: under torch.autocast("cuda") (how the reference runs, :60 / :392) that
+    # is the autocast dtype, and the concatenated weights are kept in it, so autocast has nothing left to cast per call.
     pdt = _compute_dtype(attn)
     lo = attn.__dict__.get(LORA_ATTR)
     if lo is not None and context is not None and context_tensor.shape[0] != hidden_states.shape[0]:
         context_tensor = context_tensor.expand(hidden_states.shape[0], -1, -1)      # one row of K|V per row of the assignment
-    if context is None and (w_qkv := _fused_weight(attn, ("to_q", "to_k", "to_v"), pdt)) is not None:
+    if context is None and (w_qkv := _fused_weight(attn, _QKV, pdt)) is not None:
         qkv = F.linear(hidden_states.to(pdt), w_qkv)            # self-attention: ONE GEMM, q/k/v are strided views
         if lo is not None:
             _lora_update(lo, qkv, hidden_states.to(pdt), _QKV)
         query, key, value = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
-    elif context is not None and (w_kv := _fused_weight(attn, ("to_k", "to_v"), pdt)) is not None:
-        if is_dict:
-            lazy_q = _LazyQuery(attn, hidden_states, pdt if pdt in _HALF else torch.bfloat16)      # deferred: see the symbolic-bias branch below
+    elif context is not None and (w_kv := _fused_weight(attn, _KV, pdt)) is not None:
+        if ctx is not None:
+            query = _LazyQuery(attn, hidden_states, pdt if pdt in _HALF else torch.bfloat16)      # deferred: see _plan_symbolic
         else:
             query = attn.to_q(hidden_states)
             if lo is not None:
                 _lora_update(lo, query, hidden_states, _Q)
-        kv_cache = context.get(KV_CACHE) if is_dict else None
+        kv_cache = ctx.get(KV_CACHE) if ctx is not None else None
         ent = kv_cache.get(id(attn)) if kv_cache is not None else None
         if ent is None:
             kv = F.linear(context_tensor.to(pdt), w_kv)         # cross-attention: K|V in one GEMM ...
@@ -742,145 +766,138 @@ def _attention(attn, hidden_states, context, out_linear):
             _lora_update(lo, query, hidden_states, _Q)
             _lora_update(lo, key, context_tensor, ("to_k",))
             _lora_update(lo, value, context_tensor, ("to_v",))
-    if lazy_q is not None:
-        cdt = key.dtype if key.dtype in _HALF else torch.bfloat16
-        key, value = _half(key, cdt), _half(value, cdt)
-    else:
-        cdt = query.dtype if query.dtype in _HALF else torch.bfloat16
-        query, key, value = _half(query, cdt), _half(key, cdt), _half(value, cdt)
+    lazy = isinstance(query, _LazyQuery)
+    src = key if lazy else query
+    cdt = src.dtype if src.dtype in _HALF else torch.bfloat16
+    return _Proj(hidden_states, query if lazy else _half(query, cdt), _half(key, cdt), _half(value, cdt), cdt, pdt, lo, ctx)
 
-    bias = None
-    gate = None
-    if context is not None and is_dict:
-        gate = context.get(ROW_GATE)   # folded CFG batches: per-row coefficient (1 = cond row; uncond row: 0, or negative_strength with negative regions)
-        f = context["WEIGHT_FUNCTION"]
-        n_img = hidden_states.shape[1]
-        try:
-            w = context[f"CROSS_ATTENTION_WEIGHT_{n_img}"]
-        except KeyError:
-            w = context["CROSS_ATTENTION_WEIGHT_ORIG"]
-            if not isinstance(w, int):
-                cache = context.setdefault("_PWW_ORIG_CACHE", {})
-                if n_img not in cache:
-                    cache[n_img] = _orig_weight_to_tokens(w, n_img)
-                w = cache[n_img]
-            else:
-                w = 0
-        lazy_w = ScaledW(w) if torch.is_tensor(w) and _LAZY_W else w
-        bias = f(lazy_w, context["SIGMA"], QKProxy(lazy_q if lazy_q is not None else query, key, attn.heads))
 
-    coeff = None
-    stat = None
-    scratch = None
-    parts = None
-    coeff_dev = None
-    bias_cols = 0
-    compact = None
-    gated = 0
-    slots = context.get(COEFF_SLOTS) if (context is not None and is_dict) else None
-    rec = context.get(ATTN_RECORDER) if (context is not None and is_dict) else None
+def _plan(attn, p, out_linear):
+    """Step 2 of _attention: look the weight map up, call the user's weight function and classify what it returned. The launches that produce
+    a statistic's partials and the hipGraph slot bookkeeping happen here, in call order."""
+    ctx = p.ctx
+    if ctx is None:
+        return _Plan("none", p.query)
+    gate = ctx.get(ROW_GATE)   # folded CFG batches: per-row coefficient (1 = cond row; uncond row: 0, or negative_strength with negative regions)
+    f = ctx["WEIGHT_FUNCTION"]
+    n_img = p.hidden.shape[1]
+    try:
+        w = ctx[f"CROSS_ATTENTION_WEIGHT_{n_img}"]
+    except KeyError:        # the reference's fallback (:96-101) on the full-resolution map, kept per token count
+        w = ctx["CROSS_ATTENTION_WEIGHT_ORIG"]
+        if not isinstance(w, int):
+            cache = ctx.setdefault("_PWW_ORIG_CACHE", {})
+            if n_img not in cache:
+                cache[n_img] = _orig_weight_to_tokens(w, n_img)
+            w = cache[n_img]
+    lazy_w = ScaledW(w) if torch.is_tensor(w) and _LAZY_W else w
+    bias = f(lazy_w, ctx["SIGMA"], QKProxy(p.query, p.key, attn.heads))
+    slots = ctx.get(COEFF_SLOTS)
     if isinstance(bias, LazyStat):     # a bare statistic: a per-image constant on every logit of a row cancels in softmax
         bias = None
     scoped = _symbolic_scoped(bias)
     if scoped is not None:
-        # c0 * w * g(sigma) * reduce(qk over one head / one row): the launches of libpww_hip_scope.so form the coefficient themselves
-        # (stock to_q; the row gate is the per-image factor). Whatever they do not take carries on with the tensors, as before.
+        # c0 * w * g(sigma) * reduce(qk over one head / one row): libpww_hip_scope.so forms the coefficient; what it declines goes on as tensors
         kind, scope, scalar = scoped
-        n_img, w_map = hidden_states.shape[1], bias.w
-        if _scoped_route(attn, key, w_map, kind, scope, rec, out_linear):
-            if query is None:
-                query = _half(lazy_q.get(), cdt)
+        if _scoped_route(attn, p.key, bias.w, kind, scope, ctx.get(ATTN_RECORDER), out_linear):
+            query, coeff_dev, parts = _query(p), None, None
             if slots is not None and not slots.unsupported:
-                coeff_dev = slots.site((kind, scope), scalar, w_map, (hidden_states.shape[0] * attn.heads, n_img, key.shape[1]), cdt)
+                coeff_dev = slots.site((kind, scope), scalar, bias.w, _qk_shape(attn, p), p.cdt)
             if scope == SCOPE_HEAD:
-                parts = ops.scope_head_parts(query, key, attn.heads, kind, gate=gate)
-            return ops.attention_scoped(query, key, value, attn.heads, attn.scale, w_map, kind, scope, scalar, gate=gate, parts=parts,
-                                        coeff_dev=coeff_dev), False
+                parts = ops.scope_head_parts(query, p.key, attn.heads, kind, gate=gate)
+            return _Plan("scoped", query, bias.w, gate, None, parts, None, coeff_dev, 0, None, 0, scoped)
         bias = bias.materialize()
     sym = _symbolic_scalar(bias)
     if sym is not None and (bias.stat is not None or slots is not None):
-        # c0 * w * g(sigma) [* reduce(qk)]: map, statistic selector and Python scalar go to the kernel as they are. Over
-        # the prompt tokens (M <= 128) the statistic is formed in the attention launch itself, unless the weight
-        # function already forced it to exist as a tensor. In hipGraph mode the scalar travels in a device word.
-        kind, scalar = sym
-        n_img, w_map = hidden_states.shape[1], bias.w
-        bias_cols = int(context.get(BIAS_COLS, 0) or 0)
-        gated = int(context.get(GATED_ROWS, 0) or 0) if gate is not None else 0
-        wc, ci = context.get(COMPACT_W + str(n_img)), context.get(COMPACT_IDX)
-        if torch.is_tensor(wc) and torch.is_tensor(ci) and context.get(f"CROSS_ATTENTION_WEIGHT_{n_img}") is w_map:
-            compact = (wc, ci)
-        if slots is not None and not slots.unsupported:
-            coeff_dev = slots.site(kind, scalar, w_map, (hidden_states.shape[0] * attn.heads, n_img, key.shape[1]), cdt)
-        have_stats = bias.stat is not None and bias.stat._proxy._stats is not None
-        # Q and the statistic's partials from ONE launch (the to_q GEMM with the score statistic in its epilogue): taken when the weight
-        # function left both untouched (nobody asked for the query or the statistics as tensors) and the GEMM covers the shape
-        if (lo is None and qproj_route(hidden_states.shape[-1], hidden_states.shape[-1] // attn.heads) and lazy_q is not None and not lazy_q.done and not have_stats and kind != ops.STAT_NONE and pdt in _HALF
-                and key.dtype == pdt and key.shape[1] <= ops.FUSED_MAX_KEYS and getattr(attn.to_q, "bias", None) is None):
-            wq = _fused_weight(attn, ("to_q",), pdt)
-            x = hidden_states if hidden_states.dtype == pdt else hidden_states.to(pdt)
+        return _plan_symbolic(attn, p, bias, sym, gate, slots, w)
+    family, coeff = "materialised", gate
+    if isinstance(bias, ScaledW):      # coeff * w with a tensor coefficient: keep the map, pass the coefficient vector to the kernel
+        if slots is not None:
+            slots.unsupported = True   # (sigma reached the kernel arguments through torch ops: one graph per step)
+        family, coeff, bias = "vector", _row_coefficients(bias, gate, p.hidden), bias.w
+    return _checked(attn, p, slots, w, _Plan(family, _query(p), bias, coeff))
+
+
+def _plan_symbolic(attn, p, bias, sym, gate, slots, w):
+    """c0 * w * g(sigma) [* reduce(qk)]: map, statistic selector and scalar (hipGraph mode: a device word) go to the kernel as they are."""
+    kind, scalar = sym
+    ctx, hidden, key, pdt, w_map = p.ctx, p.hidden, p.key, p.pdt, bias.w
+    n_img, M = hidden.shape[1], key.shape[1]
+    bias_cols = int(ctx.get(BIAS_COLS, 0) or 0)
+    gated = int(ctx.get(GATED_ROWS, 0) or 0) if gate is not None else 0
+    coeff_dev = parts = scratch = query = None
+    wc, ci = ctx.get(COMPACT_W + str(n_img)), ctx.get(COMPACT_IDX)
+    compact = (wc, ci) if torch.is_tensor(wc) and torch.is_tensor(ci) and ctx.get(f"CROSS_ATTENTION_WEIGHT_{n_img}") is w_map else None
+    if slots is not None and not slots.unsupported:
+        coeff_dev = slots.site(kind, scalar, w_map, _qk_shape(attn, p), p.cdt)
+    have_stats = bias.stat is not None and bias.stat._proxy._stats is not None
+    stat = (None, kind, scalar)
+    short = M <= ops.FUSED_MAX_KEYS
+    if have_stats or not (short or ops.long_keys(M)):
+        # the weight function already forced the statistics to exist as a tensor, or more keys than a pass-2-only launch takes
+        stat = (bias.stat.stats() if bias.stat is not None else None, kind, scalar)
+    else:
+        # Q and the statistic's partials from ONE launch (to_q GEMM, statistic in its epilogue): the query is untouched, the GEMM covers the shape
+        if (short and p.lo is None and qproj_route(hidden.shape[-1], hidden.shape[-1] // attn.heads) and isinstance(p.query, _LazyQuery)
+                and not p.query.done and kind != ops.STAT_NONE and pdt in _HALF and key.dtype == pdt and getattr(attn.to_q, "bias", None) is None):
+            wq = _fused_weight(attn, _Q, pdt)
+            x = hidden if hidden.dtype == pdt else hidden.to(pdt)
             if wq is not None and ops.qproj_parts(x, wq, key, attn.heads) > 0:
                 query, parts = ops.qproj_stat(x, wq, key, attn.heads, kind, gate=gate)
-                stat = (None, kind, scalar)
-        if parts is not None:
-            pass
-        elif FUSED_CROSS and not have_stats and key.shape[1] <= ops.FUSED_MAX_KEYS:
-            stat = (None, kind, scalar)
+        if parts is None and short and FUSED_CROSS:
             scratch = attn.__dict__.get("_pww_fused_scratch")
             if scratch is None:
                 scratch = attn.__dict__["_pww_fused_scratch"] = ops.FusedScratch()
-        elif not have_stats and key.shape[1] <= ops.FUSED_MAX_KEYS:
-            # the default for every layer the GEMM-epilogue route does not take: stock to_q, one small launch for the statistic's partials
-            # over the finished Q, pass-2-only attention (a statistic-free `c * w` needs no partials at all)
-            if query is None:
-                query = _half(lazy_q.get(), cdt)
-            if kind != ops.STAT_NONE:
-                parts = ops.qk_parts(query, key, attn.heads, kind, gate=gate, gated=gated)
-            stat = (None, kind, scalar)
-        elif not have_stats and ops.long_keys(key.shape[1]):
-            # a prompt encoded in 2 or 3 chunks (154 / 231 keys): the same pair of launches from libpww_hip_long.so -- stock to_q on every
-            # layer, the statistic's partials over the finished Q, pass-2-only attention over four 64-key tiles
-            if query is None:
-                query = _half(lazy_q.get(), cdt)
-            if kind != ops.STAT_NONE:
-                parts = ops.long_qk_parts(query, key, attn.heads, kind, gate=gate, gated=gated)
-            stat = (None, kind, scalar)
-        else:
-            stat = (bias.stat.stats() if bias.stat is not None else None, kind, scalar)
-        bias = w_map
-    elif isinstance(bias, ScaledW):    # coeff * w with a tensor coefficient: keep the map, pass the coefficient vector to the kernel
-        if slots is not None:
-            slots.unsupported = True   # (sigma reached the kernel arguments through torch ops: one graph per step)
-        if bias.stat is not None:
-            bias = ScaledW(bias.w, bias.coeff * bias.stat.materialize())
-        c = bias.coeff
-        B = hidden_states.shape[0]
-        if torch.is_tensor(c):
-            coeff = c.reshape(-1).to(torch.float32)
-            coeff = coeff.expand(B) if coeff.numel() == 1 else coeff
-        else:
-            coeff = torch.full((B,), float(c), dtype=torch.float32, device=hidden_states.device)
-        if gate is not None:
-            coeff = coeff * gate
-        gate = coeff
-        bias = bias.w
-    if query is None:       # (every path but the one above: the plain projection)
-        query = _half(lazy_q.get(), cdt)
+        elif parts is None and kind != ops.STAT_NONE:
+            # the default for every layer the GEMM-epilogue route does not take: stock to_q, one small launch for the statistic's partials over
+            # the finished Q (libpww_hip_long.so's for a prompt encoded in 2 or 3 chunks), pass-2-only attention; `c * w` needs no partials
+            query = _query(p)
+            parts = (ops.qk_parts if short else ops.long_qk_parts)(query, key, attn.heads, kind, gate=gate, gated=gated)
+    if query is None:
+        query = _query(p)
+    return _checked(attn, p, slots, w, _Plan("symbolic", query, w_map, gate, stat, parts, scratch, coeff_dev, bias_cols, compact, gated))
+
+
+def _row_coefficients(bias, gate, hidden):
+    """The fp32 [B] coefficient vector of a ScaledW with a tensor (or, outside hipGraph mode, Python) coefficient, times the row gate."""
+    if bias.stat is not None:
+        bias = ScaledW(bias.w, bias.coeff * bias.stat.materialize())
+    c, B = bias.coeff, hidden.shape[0]
+    if torch.is_tensor(c):
+        coeff = c.reshape(-1).to(torch.float32)
+        coeff = coeff.expand(B) if coeff.numel() == 1 else coeff
+    else:
+        coeff = torch.full((B,), float(c), dtype=torch.float32, device=hidden.device)
+    return coeff if gate is None else coeff * gate
+
+
+def _checked(attn, p, slots, w, plan):
+    """`plan` if its bias is a tensor softmax can see, else the "none" plan. hipGraph slots: a call without a bias registers a NO_BIAS site (the
+    graph holds a bias-free kernel there), a bias without `stat` depends on sigma through torch ops and marks the slots unsupported."""
+    bias = plan.bias
     if isinstance(bias, QKProxy):
-        bias = bias._materialize()
-    if not torch.is_tensor(bias) or bias.dim() == 0:
-        # python scalar / 0-dim tensor: a constant added to every logit of a row cancels in softmax
-        # (the unconditional pass returns 0.0, :493)
-        bias = None
-        if slots is not None and not slots.unsupported and is_dict:
-            # hipGraph mode: this call site is captured WITHOUT a bias kernel -- say so, or the graph would be replayed for a
-            # weight function that wants one (CoeffSlots.update re-classifies every site each step)
-            slots.site(CoeffSlots.NO_BIAS, 0.0, w, (hidden_states.shape[0] * attn.heads, hidden_states.shape[1], key.shape[1]), cdt)
-    elif slots is not None and stat is None:
-        slots.unsupported = True       # a materialised bias tensor depends on sigma through torch ops
-    if bias is None:
+        plan = plan._replace(bias=(bias := bias._materialize()))
+    if not torch.is_tensor(bias) or bias.dim() == 0:       # a constant on every logit of a row cancels in softmax (the unconditional pass returns 0.0, :493)
+        if slots is not None and not slots.unsupported:
+            slots.site(CoeffSlots.NO_BIAS, 0.0, w, _qk_shape(attn, p), p.cdt)
+        return _Plan("none", plan.query)
+    if slots is not None and plan.stat is None:
+        slots.unsupported = True
+    return plan
+
+
+def _launch(attn, p, plan, out_linear):
+    """Step 3 of _attention: the scoped launch, the attention + to_out launch or ops.attention -- with a recorder in the context, followed by
+    one probabilities launch with the same q / k / map / coefficient inputs (pww_hip.record_attention_maps)."""
+    family, query, bias, gate, stat, parts, scratch, coeff_dev, bias_cols, compact, gated, scoped = plan
+    key, value = p.key, p.value
+    if family == "scoped":
+        return ops.attention_scoped(query, key, value, attn.heads, attn.scale, bias, *scoped, gate=gate, parts=parts, coeff_dev=coeff_dev), False
+    rec = p.ctx.get(ATTN_RECORDER) if p.ctx is not None else None
+    if family == "none":
         out = ops.attention(query, key, value, attn.heads, attn.scale)
         if rec is not None:
-            _record_probs(rec, attn, context, query, key, None, None, None, None)
+            _record_probs(rec, attn, p.ctx, query, key, None, None, None, None)
         return out, False
     if (out_linear is not None and stat is not None and stat[0] is None and scratch is None and key.shape[1] <= ops.FUSED_MAX_KEYS
             and out_linear.weight.dtype == query.dtype and ops.attention_out_supported(query, key, attn.heads, bias, out_linear.weight, bias_cols)):
@@ -893,22 +910,18 @@ def _attention(attn, hidden_states, context, out_linear):
     if rec is None:
         return ops.attention(query, key, value, attn.heads, attn.scale, bias=bias, bias_coeff=gate, stat=stat, scratch=scratch,
                              coeff_dev=coeff_dev, bias_cols=bias_cols, compact=compact, gated=gated, parts=parts), False
-    # recording (pww_hip.record_attention_maps): the same launch, then one probabilities launch with the same q / k / map / coefficient
-    # inputs. The "parts" route folds its statistic inside the attention launch: that launch is asked to hand the folded fields out.
-    route = ops._attention_route(True, stat, scratch, parts, key.shape[1])
-    if stat is not None and stat[0] is None and scratch is None and ops.long_keys(key.shape[1]):
-        route = "parts"     # (ops.attention's "long" route: the parts contract over 129 .. 256 keys)
+    # recording: the "parts" and "long" routes fold their statistic inside the attention launch, which is asked to hand the folded fields out
+    route = ops.attention_route(True, stat, scratch, parts, key.shape[1])
+    folds = route in ("parts", "long")
     stats_out = None
-    if route == "parts" and stat[1] != ops.STAT_NONE and not rec.muted:
+    if folds and stat[1] != ops.STAT_NONE and not rec.muted:
         stats_out = torch.empty((query.shape[0], 4), dtype=torch.float64, device=query.device)
     out = ops.attention(query, key, value, attn.heads, attn.scale, bias=bias, bias_coeff=gate, stat=stat, scratch=scratch, stats_out=stats_out,
                         coeff_dev=coeff_dev, bias_cols=bias_cols, compact=compact, gated=gated, parts=parts)
     if route == "fused":
         _warn_once("record_fused", "attention maps: the in-launch statistic route of the experiments library (PWW_FUSED_CROSS=1) is not recorded")
-    elif route == "parts":
-        _record_probs(rec, attn, context, query, key, bias, gate, (stats_out, stat[1], stat[2]), coeff_dev)
-    else:       # "plain": c[b] = gate[b]; "stat": the [B, 4] statistics came with the call
-        _record_probs(rec, attn, context, query, key, bias, gate, stat, coeff_dev)
+    else:       # "plain": c[b] = gate[b]; "stat": the [B, 4] statistics came with the call; "parts" / "long": the launch handed them out
+        _record_probs(rec, attn, p.ctx, query, key, bias, gate, (stats_out, stat[1], stat[2]) if folds else stat, coeff_dev)
     return out, False
 
 

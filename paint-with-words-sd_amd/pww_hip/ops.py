@@ -269,6 +269,15 @@ def _attention_route(has_bias, stat, scratch, parts, M):
     return "parts" if scratch is None else "fused"
 
 
+def attention_route(has_bias, stat, scratch, parts, M):
+    """The launch attention() takes for these arguments and M keys: _attention_route's table, then by key count alone "long" -- the pair of
+    launches of libpww_hip_long.so, which holds the parts contract over FUSED_MAX_KEYS < M <= LONG_MAX_KEYS."""
+    route = _attention_route(has_bias, stat, scratch, parts, M)
+    if route in ("parts", "stat") and stat[0] is None and scratch is None and long_keys(M):
+        return "long"
+    return route
+
+
 def _launch_stat(lib, io, bias, coeff, d, stat, coeff_dev):
     """c[b] = scalar * stat(stats[b]) * coeff[b]; null stats (STAT_NONE): the scalar -- or the hipGraph mode's device word -- alone."""
     stats, kind, scalar = stat
@@ -278,12 +287,25 @@ def _launch_stat(lib, io, bias, coeff, d, stat, coeff_dev):
                                               ctypes.byref(d), _opt_ref(op), _stream()), "pww_cross_attn_fwd_stat_ex")
 
 
-def _launch_parts(lib, io, bias, coeff, d, stat, parts, stats_out, coeff_dev, bias_cols, compact, gated):
-    """Pass 2 only: the statistic's partials came from qproj_stat / qk_parts (none needed for STAT_NONE); nothing in it waits for another workgroup."""
+def _parts_stat(d, stat, parts, missing):
+    """(kind, scalar) of stat = (None, kind, scalar) for a launch that folds `parts`: a statistic without its partials raises `missing`."""
     _, kind, scalar = stat
     if kind != STAT_NONE and parts is None:
-        raise PwwHipError("a statistic formed outside the attention launch needs its partials (qproj_stat / qk_parts), or a FusedScratch for the in-launch form")
+        raise PwwHipError(missing)
     _check_f64(parts, "parts", d.B, "nparts", 4)
+    return kind, scalar
+
+
+def _parts_args(io, bias, coeff, d, kind, scalar, parts, stats_out, op):
+    """The arguments pww_cross_attn_fwd_parts and pww_long_cross_attn_fwd_parts share."""
+    return (*io, _ptr(bias), int(kind), float(scalar), _ptr(coeff), ctypes.byref(d), _ptr(parts), int(parts.shape[1]) if parts is not None else 0,
+            _ptr(stats_out), _opt_ref(op), _stream())
+
+
+def _launch_parts(lib, io, bias, coeff, d, stat, parts, stats_out, coeff_dev, bias_cols, compact, gated):
+    """Pass 2 only: the statistic's partials came from qproj_stat / qk_parts (none needed for STAT_NONE); nothing in it waits for another workgroup."""
+    kind, scalar = _parts_stat(d, stat, parts, "a statistic formed outside the attention launch needs its partials (qproj_stat / qk_parts), or a "
+                                               "FusedScratch for the in-launch form")
     if d.M > FUSED_MAX_KEYS:
         raise PwwHipError("the pass-2-only cross-attention launch takes at most %d keys (partials over more keys: fold them with "
                           "fold_parts and pass stat=(stats, kind, scalar))" % FUSED_MAX_KEYS)
@@ -291,9 +313,7 @@ def _launch_parts(lib, io, bias, coeff, d, stat, parts, stats_out, coeff_dev, bi
     if compact is not None and (compact[0].shape[-1] > COMPACT_MAX_R or not _lib.has_experiments()):
         compact = None          # (the compact form of the map is an experiments-library form: the dense map serves)
     op = _cross_opts(d.B, d.N, coeff_dev, bias_cols, compact, gated)
-    _lib.check(lib.pww_cross_attn_fwd_parts(*io, _ptr(bias), int(kind), float(scalar), _ptr(coeff), ctypes.byref(d), _ptr(parts),
-                                            int(parts.shape[1]) if parts is not None else 0, _ptr(stats_out), _opt_ref(op), _stream()),
-               "pww_cross_attn_fwd_parts")
+    _lib.check(lib.pww_cross_attn_fwd_parts(*_parts_args(io, bias, coeff, d, kind, scalar, parts, stats_out, op)), "pww_cross_attn_fwd_parts")
 
 
 def long_keys(M):
@@ -303,12 +323,8 @@ def long_keys(M):
 
 def _launch_long(io, bias, coeff, d, stat, parts, stats_out, coeff_dev, bias_cols, gated):
     """_launch_parts for FUSED_MAX_KEYS < M <= LONG_MAX_KEYS: pww_long_cross_attn_fwd_parts (partials from long_qk_parts; none for STAT_NONE).
-    The compact form of the map is an experiments-library form of the <= 128-key kernel; ops.attention does not hand it on: here the dense
-    map, which every caller passes beside it, serves (as in _launch_parts on the product library)."""
-    _, kind, scalar = stat
-    if kind != STAT_NONE and parts is None:
-        raise PwwHipError("a statistic over %d keys needs its partials (long_qk_parts)" % d.M)
-    _check_f64(parts, "parts", d.B, "nparts", 4)
+    The compact form of the map belongs to the <= 128-key kernel of the experiments library: ops.attention does not hand it on, the dense map serves."""
+    kind, scalar = _parts_stat(d, stat, parts, "a statistic over %d keys needs its partials (long_qk_parts)" % d.M)
     _check_f64(stats_out, "stats_out", d.B, 4)
     op = _cross_opts(d.B, d.N, coeff_dev, bias_cols, None, gated)
     lib = _lib.load_long()
@@ -318,8 +334,7 @@ def _launch_long(io, bias, coeff, d, stat, parts, stats_out, coeff_dev, bias_col
     if parts is not None and parts.shape[1] != want:
         raise PwwHipError("cross-attention over %d keys folds the partials of long_qk_parts (%d per image for this problem), got %d: the pass-2-only "
                           "launch of libpww_hip.so takes at most %d keys" % (d.M, want, parts.shape[1], FUSED_MAX_KEYS))
-    _lib.check(lib.pww_long_cross_attn_fwd_parts(*io, _ptr(bias), int(kind), float(scalar), _ptr(coeff), ctypes.byref(d), _ptr(parts),
-                                                 int(parts.shape[1]) if parts is not None else 0, _ptr(stats_out), _opt_ref(op), _stream()),
+    _lib.check(lib.pww_long_cross_attn_fwd_parts(*_parts_args(io, bias, coeff, d, kind, scalar, parts, stats_out, op)),
                "pww_long_cross_attn_fwd_parts", lib)
 
 
@@ -360,9 +375,7 @@ def attention(q, k, v, heads, scale, bias=None, bias_coeff=None, stat=None, scra
     out = torch.empty((B, N, C), dtype=q.dtype, device=q.device)
     d = _desc(q, k, v, out, heads, scale)
     lib = _lib.load()
-    route = _attention_route(bias is not None, stat, scratch, parts, d.M)
-    if route in ("parts", "stat") and stat[0] is None and scratch is None and long_keys(d.M):
-        route = "long"      # by key count alone: the pair of launches of libpww_hip_long.so
+    route = attention_route(bias is not None, stat, scratch, parts, d.M)
     io = (_ptr(q), _ptr(k), _ptr(v), _ptr(out))
     if route != "self":
         bias = _bias_view(bias, d)
@@ -480,12 +493,9 @@ def attention_out(q, k, v, heads, scale, bias, weight, weight_bias=None, residua
     d = _desc(q, k, v, out, heads, scale)
     bias = _bias_view(bias, d)
     bias_coeff = _per_image_f32(bias_coeff, B, "bias_coeff", expand=True)
-    kind, scalar = (STAT_NONE, 1.0) if stat is None else (stat[1], stat[2])
     if stat is not None and stat[0] is not None:
         raise PwwHipError("attention_out folds partials (stat = (None, kind, scalar), parts = qproj_stat / qk_parts output)")
-    if kind != STAT_NONE and parts is None:
-        raise PwwHipError("attention_out: a statistic needs its partials (qproj_stat / qk_parts)")
-    _check_f64(parts, "parts", B, "nparts", 4)
+    kind, scalar = _parts_stat(d, stat or (None, STAT_NONE, 1.0), parts, "attention_out: a statistic needs its partials (qproj_stat / qk_parts)")
     _check_f64(stats_out, "stats_out", B, 4)
     op = _cross_opts(B, N, coeff_dev, bias_cols, None, gated)
     rs = (ctypes.c_int64 * 2)(residual.stride(0), residual.stride(1)) if residual is not None else None
@@ -549,47 +559,39 @@ def qproj_stat(x, weight, k, heads, kind, gate=None):
     return q, parts
 
 
+def _stat_parts(name, load, q, k, heads, kind, gate, gated=0, per_head=False):
+    """The body of qk_parts, long_qk_parts and scope_head_parts (`name`): the library `load()` returns holds the launch pww_<name> and its
+    count query pww_<name>_count. per_head: partials per (image, head) -- [B, heads, nparts, 4] -- and a launch without the `gated` hint."""
+    _require_gpu(q, k, gate)
+    if q.dtype != k.dtype:
+        raise PwwHipError("%s: dtypes differ: %s %s" % (name, q.dtype, k.dtype))
+    q, k = _prep(q), _prep(k)
+    d = _desc(q, k, None, None, heads, 1.0)
+    lib = load()
+    nparts = int(getattr(lib, "pww_%s_count" % name)(ctypes.byref(d)))
+    if nparts <= 0:
+        raise PwwHipError("%s: unsupported problem %s x %s, %d heads" % (name, tuple(q.shape), tuple(k.shape), heads))
+    B = q.shape[0]
+    parts = torch.empty((B, heads, nparts, 4) if per_head else (B, nparts, 4), dtype=torch.float64, device=q.device)
+    gate = _per_image_f32(gate, B, "gate")
+    hint = () if per_head else (int(gated or 0),)
+    with torch.cuda.device(q.device):
+        _lib.check(getattr(lib, "pww_" + name)(_ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), *hint, _ptr(parts), parts.numel() * 8, _stream()),
+                   "pww_" + name, lib)
+    return parts
+
+
 def qk_parts(q, k, heads, kind, gate=None, gated=0):
     """Partials of the per-image score statistic of q k^T over a FINISHED q (paint_with_words.py:87 + the reduction weight_function
     applies): float64 [B, nparts, 4], the input of attention(..., parts=...). One small launch (pww_qk_parts): the layers whose to_q
     stays the stock GEMM. gate: optional fp32 [B] (images with gate 0 get no partials); gated: hint that exactly the first `gated`
     images have a non-zero gate."""
-    _require_gpu(q, k, gate)
-    if q.dtype != k.dtype:
-        raise PwwHipError("qk_parts: dtypes differ: %s %s" % (q.dtype, k.dtype))
-    q, k = _prep(q), _prep(k)
-    d = _desc(q, k, None, None, heads, 1.0)
-    lib = _lib.load()
-    nparts = int(lib.pww_qk_parts_count(ctypes.byref(d)))
-    if nparts <= 0:
-        raise PwwHipError("qk_parts: unsupported problem %s x %s, %d heads" % (tuple(q.shape), tuple(k.shape), heads))
-    B = q.shape[0]
-    parts = torch.empty((B, nparts, 4), dtype=torch.float64, device=q.device)
-    gate = _per_image_f32(gate, B, "gate")
-    with torch.cuda.device(q.device):
-        _lib.check(lib.pww_qk_parts(_ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), int(gated or 0), _ptr(parts), parts.numel() * 8, _stream()),
-                   "pww_qk_parts")
-    return parts
+    return _stat_parts("qk_parts", _lib.load, q, k, heads, kind, gate, gated)
 
 
 def long_qk_parts(q, k, heads, kind, gate=None, gated=0):
     """qk_parts for FUSED_MAX_KEYS < M <= LONG_MAX_KEYS (pww_long_qk_parts): float64 [B, nparts, 4], the input of attention(..., parts=...)."""
-    _require_gpu(q, k, gate)
-    if q.dtype != k.dtype:
-        raise PwwHipError("long_qk_parts: dtypes differ: %s %s" % (q.dtype, k.dtype))
-    q, k = _prep(q), _prep(k)
-    d = _desc(q, k, None, None, heads, 1.0)
-    lib = _lib.load_long()
-    nparts = int(lib.pww_long_qk_parts_count(ctypes.byref(d)))
-    if nparts <= 0:
-        raise PwwHipError("long_qk_parts: unsupported problem %s x %s, %d heads" % (tuple(q.shape), tuple(k.shape), heads))
-    B = q.shape[0]
-    parts = torch.empty((B, nparts, 4), dtype=torch.float64, device=q.device)
-    gate = _per_image_f32(gate, B, "gate")
-    with torch.cuda.device(q.device):
-        _lib.check(lib.pww_long_qk_parts(_ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), int(gated or 0), _ptr(parts), parts.numel() * 8, _stream()),
-                   "pww_long_qk_parts", lib)
-    return parts
+    return _stat_parts("long_qk_parts", _lib.load_long, q, k, heads, kind, gate, gated)
 
 
 SCOPE_HEAD, SCOPE_ROW = _lib.SCOPE_HEAD, _lib.SCOPE_ROW   # PWW_SCOPE_* of include/pww_hip_scope.h
@@ -613,22 +615,7 @@ def scope_head_parts(q, k, heads, kind, gate=None):
     """Partials of the score statistic of q k^T PER (image, head) over a finished q: float64 [B, heads, nparts, 4] = (max, min, sum, sum of
     squares), the input of attention_scoped(..., scope=SCOPE_HEAD, parts=...). One small launch (pww_scope_head_parts, M <= 128).
     gate: optional fp32 [B]; images with gate 0 get no partials (their rows are left as allocated)."""
-    _require_gpu(q, k, gate)
-    if q.dtype != k.dtype:
-        raise PwwHipError("scope_head_parts: dtypes differ: %s %s" % (q.dtype, k.dtype))
-    q, k = _prep(q), _prep(k)
-    d = _desc(q, k, None, None, heads, 1.0)
-    lib = _scope_lib()
-    nparts = int(lib.pww_scope_head_parts_count(ctypes.byref(d)))
-    if nparts <= 0:
-        raise PwwHipError("scope_head_parts: unsupported problem %s x %s, %d heads" % (tuple(q.shape), tuple(k.shape), heads))
-    B = q.shape[0]
-    parts = torch.empty((B, heads, nparts, 4), dtype=torch.float64, device=q.device)
-    gate = _per_image_f32(gate, B, "gate")
-    with torch.cuda.device(q.device):
-        _lib.check(lib.pww_scope_head_parts(_ptr(q), _ptr(k), _ptr(gate), ctypes.byref(d), int(kind), _ptr(parts), parts.numel() * 8, _stream()),
-                   "pww_scope_head_parts", lib)
-    return parts
+    return _stat_parts("scope_head_parts", _scope_lib, q, k, heads, kind, gate, per_head=True)
 
 
 def attention_scoped(q, k, v, heads, scale, bias, kind, scope, scalar, gate=None, parts=None, stats_out=None, coeff_dev=None):

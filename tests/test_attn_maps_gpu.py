@@ -146,7 +146,7 @@ def test_recorded_coefficient_through_the_plug(gpu_device, route, shape):
 
     def spy(*a, **kw):
         used.append((a[0], a[1]))
-        seen.append(pww_hip.ops._attention_route(kw.get("bias") is not None, kw.get("stat"), kw.get("scratch"), kw.get("parts"), a[1].shape[1])
+        seen.append(pww_hip.ops.attention_route(kw.get("bias") is not None, kw.get("stat"), kw.get("scratch"), kw.get("parts"), a[1].shape[1])
                     + ("+parts" if kw.get("parts") is not None else ""))
         return real(*a, **kw)
 
