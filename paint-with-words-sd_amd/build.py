@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Nine libraries come out of the same sources:
+Ten libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
                               measured and not made a default (include/pww_hip.h, section "experiments"). Built by the tests / tools that
@@ -22,6 +22,7 @@ Nine libraries come out of the same sources:
                                 convtail  conv2 of a ResnetBlock2D with the block's 1 x 1 shortcut as further K-slabs (csrc/pww_conv_tail.hip)
                               and SIDE_LIBS_EXTRA, the open-ended home of every later side library:
                                 canvas    canvases larger than the UNet's window: the gather of the windows and the combine of their noise predictions
+                                concat    the up blocks without torch.cat: GroupNorm and conv2 + shortcut reading the two halves of the concatenation in place
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -61,6 +62,7 @@ SIDE_LIBS_CONV = {
 # side library is a row here and in the loader's SIDE_EXTRA, whatever it is for)
 SIDE_LIBS_EXTRA = {
     "canvas": ("pww_canvas.hip", [], "canvases larger than the UNet's window: the windows' gather and the combine of their noise predictions"),
+    "concat": ("pww_concat.hip", [], "the up blocks without torch.cat: GroupNorm and conv2 + shortcut over the two halves of the concatenation"),
 }
 ALL_SIDE_LIBS = {**SIDE_LIBS, **SIDE_LIBS_CONV, **SIDE_LIBS_EXTRA}
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
@@ -71,6 +73,7 @@ LIB_LONG, LIB_SCOPE, LIB_LINEAR, LIB_REGIONS, LIB_LORA = (SIDE_PATHS[n] for n in
 LONG_UNITS, SCOPE_UNITS, LINEAR_UNITS, REGIONS_UNITS, LORA_UNITS = (SIDE_UNITS[n] for n in ("long", "scope", "linear", "regions", "lora"))
 LIB_CONVTAIL, CONVTAIL_UNITS = SIDE_PATHS["convtail"], SIDE_UNITS["convtail"]
 LIB_CANVAS, CANVAS_UNITS = SIDE_PATHS["canvas"], SIDE_UNITS["canvas"]
+LIB_CONCAT, CONCAT_UNITS = SIDE_PATHS["concat"], SIDE_UNITS["concat"]
 SIDE_PUBLIC_HEADERS = {"canvas": ["pww_hip_regions.h"]}       # include/ headers a side library's own header includes (besides pww_hip.h)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
@@ -156,6 +159,7 @@ def build_regions(force=False, verbose=False): return build_side("regions", forc
 def build_lora(force=False, verbose=False): return build_side("lora", force, verbose)  # noqa: E704
 def build_convtail(force=False, verbose=False): return build_side("convtail", force, verbose)  # noqa: E704
 def build_canvas(force=False, verbose=False): return build_side("canvas", force, verbose)  # noqa: E704
+def build_concat(force=False, verbose=False): return build_side("concat", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):

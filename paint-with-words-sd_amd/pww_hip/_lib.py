@@ -29,6 +29,9 @@ CONVTAIL_LIB_PATH = os.environ.get("PWW_HIP_CONVTAIL_LIB", os.path.join(_HERE, "
 #   canvas    canvases larger than the UNet's window: the gather of the windows and the combine of their noise predictions
 #             (include/pww_hip_canvas.h): ops.canvas_gather, ops.canvas_combine. Its spec is in SIDE_EXTRA below.
 CANVAS_LIB_PATH = os.environ.get("PWW_HIP_CANVAS_LIB", os.path.join(_HERE, "libpww_hip_canvas.so"))
+#   concat    the up blocks without torch.cat: GroupNorm and conv2 + shortcut reading the two halves of the concatenation where they lie
+#             (include/pww_hip_concat.h): ops.group_norm_cat, ops.conv3x3_shortcut_cat. Its spec is in SIDE_EXTRA below.
+CONCAT_LIB_PATH = os.environ.get("PWW_HIP_CONCAT_LIB", os.path.join(_HERE, "libpww_hip_concat.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -91,6 +94,12 @@ CONVTAIL_MIN_VERSION = 100
 CANVAS_EXPORTS = ("pww_canvas_version", "pww_canvas_last_error", "pww_canvas_gather", "pww_canvas_combine")
 CANVAS_MIN_VERSION = 100
 CANVAS_MAX_WINDOWS, CANVAS_MAX_RAMP, CANVAS_MIN_WINDOW, CANVAS_MAX_WINDOW = 64, 64, 8, 128      # PWW_CANVAS_* of the header
+
+
+# every symbol include/pww_hip_concat.h declares for libpww_hip_concat.so
+CONCAT_EXPORTS = ("pww_concat_version", "pww_concat_last_error", "pww_concat_group_norm_workspace_bytes", "pww_concat_group_norm_fwd",
+                  "pww_concat_convtail_workspace_bytes", "pww_concat_convtail_fwd")
+CONCAT_MIN_VERSION = 100
 
 
 class AttnDesc(ctypes.Structure):
@@ -159,6 +168,19 @@ class ConvTailDesc(ctypes.Structure):
     """struct pww_convtail_desc (3 x 3 convolution + 1 x 1 shortcut as one implicit GEMM; size-prefixed)."""
     _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
                 ("Cin", ctypes.c_int32), ("C2", ctypes.c_int32), ("Cout", ctypes.c_int32), ("tile_n", ctypes.c_int32), ("splitk", ctypes.c_int32)]
+
+
+class ConcatGnDesc(ctypes.Structure):
+    """struct pww_concat_gn_desc (GroupNorm over two channels_last tensors laid end to end; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("C1", ctypes.c_int32), ("C2", ctypes.c_int32),
+                ("HW", ctypes.c_int32), ("G", ctypes.c_int32), ("eps", ctypes.c_float), ("act", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class ConcatTailDesc(ctypes.Structure):
+    """struct pww_concat_tail_desc (pww_convtail_desc with the shortcut's input in two parts; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("Cin", ctypes.c_int32), ("C1", ctypes.c_int32), ("C2", ctypes.c_int32), ("Cout", ctypes.c_int32), ("tile_n", ctypes.c_int32),
+                ("splitk", ctypes.c_int32), ("_pad", ctypes.c_int32)]
 
 
 class Region(ctypes.Structure):
@@ -351,6 +373,12 @@ SIDE_EXTRA = {
     "canvas": dict(path="CANVAS_LIB_PATH", exports=CANVAS_EXPORTS, min_version=CANVAS_MIN_VERSION, missing_ok=False, needs="canvases larger than the window need it", sigs={
         "pww_canvas_gather": ([_vp, _vp, _P(_i32), _i32, _P(_i32), _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _i32, _vp], _int),
         "pww_canvas_combine": ([_vp, _vp, _vp, _vp, _f32, _vp, _P(_i32), _i32, _P(_i32), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp], _int)}),
+    # missing_ok: the caller materialises torch.cat and runs the one-source ops, which compute the same bits
+    "concat": dict(path="CONCAT_LIB_PATH", exports=CONCAT_EXPORTS, min_version=CONCAT_MIN_VERSION, missing_ok=True, needs="the up blocks without torch.cat need it", sigs={
+        "pww_concat_group_norm_workspace_bytes": ([_P(ConcatGnDesc)], _sz),
+        "pww_concat_group_norm_fwd": ([_vp, _vp, _vp, _vp, _vp, _P(ConcatGnDesc), _vp, _sz, _vp], _int),
+        "pww_concat_convtail_workspace_bytes": ([_P(ConcatTailDesc)], _sz),
+        "pww_concat_convtail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(ConcatTailDesc), _vp, _sz, _vp], _int)}),
 }
 _side = {}      # name -> loaded handle
 
@@ -430,6 +458,11 @@ def load_convtail():
 def load_canvas():
     lib = _side.get("canvas")
     return lib if lib is not None else load_side("canvas")
+
+
+def load_concat():
+    lib = _side.get("concat")
+    return lib if lib is not None else load_side("concat")
 
 
 class experiments:

@@ -16,6 +16,10 @@ Installed per INSTANCE (``module.forward = ...``; ``nn.Module.__call__`` and its
   The biases of ``conv1`` / ``conv2`` ride along as operands of the next fused op (``pre_bias`` of norm2, ``ops.bias_residual`` for the block's
   output) instead of costing an add launch each. A block that changes its channel count runs ``conv_shortcut(x) + conv2(h)`` as ONE implicit
   GEMM (``ops.conv3x3_shortcut``: the 1 x 1 shortcut as further K-slabs of conv2's kernel) where ``_conv_shortcut_route`` says so.
+* ``UpBlock`` (the stand-in) / ``UpBlock2D`` / ``CrossAttnUpBlock2D`` (diffusers 0.10.0) -- the forward restated without
+  ``torch.cat([hidden_states, skip], 1)``: each resnet gets the PAIR, and where ``_resnet_cat`` says so its ``norm1`` and its conv2 + shortcut
+  read the two tensors where they lie (``ops.group_norm_cat``, ``ops.conv3x3_shortcut_cat``: the same bits as on the concatenated tensor).
+  Everything else materialises the concatenation and calls the resnet exactly as the stock block does.
 * every other ``nn.GroupNorm`` of the model (``Transformer2DModel.norm``, ``conv_norm_out``) -- the same kernels without addend / activation.
 * ``BasicTransformerBlock`` -- ``attn(norm(h)) + h`` and the block's NEXT LayerNorm as one launch (``ops.add_layer_norm``); ``GEGLU`` --
   ``x * gelu(gate)`` as one launch behind its projection; 1 x 1 ``nn.Conv2d`` (``proj_in`` / ``proj_out`` / ``conv_shortcut``) on channels_last
@@ -46,6 +50,9 @@ CONV3X3 = os.environ.get("PWW_CONV3X3", "1") != "0"      # A/B: 3 x 3 convolutio
 # A/B: the 1 x 1 conv_shortcut of a ResnetBlock2D as further K-slabs of conv2's implicit GEMM (csrc/pww_conv_tail.hip); "0": the 1 x 1 GEMM
 # writes its tensor and conv2's epilogue reads it as the residual
 CONV_SHORTCUT = os.environ.get("PWW_CONV_SHORTCUT", "1") != "0"
+# A/B: the up blocks without `torch.cat([x, skip], 1)`: norm1 and conv2 + shortcut of each of their ResnetBlock2D read the two tensors where they
+# lie (csrc/pww_concat.hip); "0": the block's own forward concatenates and the one-source ops run -- the same bits either way
+CONCAT = os.environ.get("PWW_CONCAT", "1") != "0"
 
 
 # ---- what the plug did with the calls it saw (a call the kernels decline must not go unnoticed) ----------------
@@ -53,8 +60,8 @@ CONV_SHORTCUT = os.environ.get("PWW_CONV_SHORTCUT", "1") != "0"
 # passes and while a hipGraph is captured (a replay runs no Python). `stats()` returns a copy, `reset_stats()` zeroes; the first decline of
 # a HIP half-precision tensor per (op, reason) also warns once -- under torch.autocast, the reference's own run mode, the whole plug steps
 # aside (autocast runs the norms in fp32) and that is worth knowing when a benchmark claims the fused blocks.
-_STATS = {k: [0, 0] for k in ("group_norm", "resnet_block", "transformer_block", "geglu", "conv1x1", "conv3x3", "linear", "conv_shortcut")}
-_UNRATED = ("conv1x1", "conv3x3", "linear", "conv_shortcut")
+_STATS = {k: [0, 0] for k in ("group_norm", "resnet_block", "transformer_block", "geglu", "conv1x1", "conv3x3", "linear", "conv_shortcut", "concat")}
+_UNRATED = ("conv1x1", "conv3x3", "linear", "conv_shortcut", "concat")
 _warned = set()
 
 
@@ -63,7 +70,8 @@ def stats():
     and 3 x 3 convolutions are listed but not rated: an NCHW tensor keeps MIOpen's convolution by the caller's choice of memory format, and
     the UNet's conv_in / conv_out have channel counts the kernel has no tile for; `linear` counts the GEMMs that were offered to the HIP
     linear kernel: "declined" ones run as the stock GEMM by the measured route table; `conv_shortcut` counts the ResnetBlock2D calls that have
-    a conv_shortcut: "fused" ones ran it inside conv2's kernel, "declined" ones as the 1 x 1 GEMM in front of conv2)."""
+    a conv_shortcut: "fused" ones ran it inside conv2's kernel, "declined" ones as the 1 x 1 GEMM in front of conv2; `concat` counts the
+    ResnetBlock2D calls of the restated up blocks: "fused" ones read (x, skip) in place, "declined" ones got torch.cat([x, skip], 1))."""
     out = {k: {"fused": v[0], "declined": v[1]} for k, v in _STATS.items()}
     rated = [v for k, v in _STATS.items() if k not in _UNRATED]
     tot = sum(v[0] + v[1] for v in rated)
@@ -198,9 +206,20 @@ def _resnet_forward(self, *args, **kwargs):
         _count("resnet_block", False, input_tensor, ("a call beyond (input_tensor, temb): %d positional, keywords %s" % (len(args), sorted(kwargs))) if not covered else _why_not(input_tensor))
         return self._pww_orig_forward(*args, **kwargs)
     temb = args[1] if len(args) == 2 else kwargs.get("temb")
+    return _resnet_body(self, input_tensor, temb)
+
+
+def _resnet_body(self, input_tensor, temb, pair=None):
+    """The restated forward behind `_resnet_forward`'s argument checks. pair = (x1, x2): the input is torch.cat([x1, x2], 1), which
+    `_resnet_cat` found both of its readers able to take in two parts (input_tensor is None then, and is only made if conv2 + shortcut
+    decline after all)."""
     _count("resnet_block", True)
-    fold = FOLD_CONV_BIAS and _plain_conv(self.conv1) and _plain_conv(self.conv2) and self.conv1.bias.dtype == input_tensor.dtype
-    h = fused_group_norm(self.norm1, input_tensor, act="silu")
+    dtype = pair[0].dtype if pair is not None else input_tensor.dtype
+    fold = FOLD_CONV_BIAS and _plain_conv(self.conv1) and _plain_conv(self.conv2) and self.conv1.bias.dtype == dtype
+    if pair is not None:
+        h = ops.group_norm_cat(pair[0], pair[1], self.norm1.num_groups, self.norm1.weight, self.norm1.bias, self.norm1.eps, act="silu")
+    else:
+        h = fused_group_norm(self.norm1, input_tensor, act="silu")
     if fold and _conv3x3_route(self.conv1, h):
         h = ops.conv3x3(h, self.conv1.weight)
     else:
@@ -225,6 +244,14 @@ def _resnet_forward(self, *args, **kwargs):
         h = dropout(h)
     scale = getattr(self, "output_scale_factor", 1.0)
     shortcut = getattr(self, "conv_shortcut", None)
+    if pair is not None:
+        took = shortcut is not None and _conv_shortcut_route(self, shortcut, h, None, fold, scale, pair=pair)
+        _STATS["concat"][0 if took else 1] += 1
+        if took:
+            return ops.conv3x3_shortcut_cat(h, self.conv2.weight, self.conv2.bias, pair[0], pair[1], shortcut.weight, shortcut.bias)
+        input_tensor = torch.cat(pair, dim=1)         # (what `_resnet_cat` could not foresee: the one-source sequence from here on)
+        if shortcut is not None:
+            _STATS["conv_shortcut"][1] -= 1           # (asked again below)
     if shortcut is not None:
         if _conv_shortcut_route(self, shortcut, h, input_tensor, fold, scale):
             return ops.conv3x3_shortcut(h, self.conv2.weight, self.conv2.bias, input_tensor, shortcut.weight, shortcut.bias)        # conv2 and the shortcut: one GEMM
@@ -258,19 +285,26 @@ def _conv3x3_route(conv, x, upsample=False):
     return ok
 
 
-def _conv_shortcut_route(block, shortcut, h, x, fold, scale):
+def _conv_shortcut_route(block, shortcut, h, x, fold, scale, pair=None):
     """Whether `conv_shortcut(x) + conv2(h)` of this ResnetBlock2D call runs as ONE implicit GEMM (ops.conv3x3_shortcut); counts the call
     either way (not rated). It does when the shortcut is a plain 1 x 1 nn.Conv2d with a bias whose forward is its own or this plug's, x is
     a channels_last tensor of the block's dtype, conv2 would take the HIP route with its bias folded, nothing is divided afterwards, and
-    the side library is there. A decline leaves today's sequence: the 1 x 1 GEMM, then conv2 with the residual in its epilogue."""
+    the side library is there. A decline leaves today's sequence: the 1 x 1 GEMM, then conv2 with the residual in its epilogue.
+    pair = (x1, x2) instead of x: the same question for x = torch.cat([x1, x2], 1) read in two parts (ops.conv3x3_shortcut_cat)."""
     own = shortcut.__dict__.get("forward")
     ok = (CONV_SHORTCUT and fold and scale == 1.0 and _is_conv1x1(shortcut) and shortcut.bias is not None
           and (own is None or getattr(own, "__func__", None) is _conv1x1_forward) and not shortcut._forward_hooks and not shortcut._forward_pre_hooks
-          and torch.is_tensor(x) and x.dim() == 4 and x.dtype == h.dtype == shortcut.weight.dtype == shortcut.bias.dtype
-          and x.is_contiguous(memory_format=torch.channels_last)
-          and not (torch.is_grad_enabled() and (x.requires_grad or shortcut.weight.requires_grad))
-          and _is_conv3x3(block.conv2) and block.conv2.stride == (1, 1) and ops.conv3x3_shortcut_takes(h, block.conv2.weight, x, shortcut.weight)
-          and ops._lib.load_convtail() is not None)
+          and _is_conv3x3(block.conv2) and block.conv2.stride == (1, 1))
+    if ok and pair is not None:
+        ok = (all(t.dtype == h.dtype == shortcut.weight.dtype == shortcut.bias.dtype for t in pair)
+              and not (torch.is_grad_enabled() and (pair[0].requires_grad or pair[1].requires_grad or shortcut.weight.requires_grad))
+              and ops.conv3x3_shortcut_cat_takes(h, block.conv2.weight, pair[0], pair[1], shortcut.weight))
+    elif ok:
+        ok = (torch.is_tensor(x) and x.dim() == 4 and x.dtype == h.dtype == shortcut.weight.dtype == shortcut.bias.dtype
+              and x.is_contiguous(memory_format=torch.channels_last)
+              and not (torch.is_grad_enabled() and (x.requires_grad or shortcut.weight.requires_grad))
+              and ops.conv3x3_shortcut_takes(h, block.conv2.weight, x, shortcut.weight)
+              and ops._lib.load_convtail() is not None)
     if ok:
         ok = _conv3x3_route(block.conv2, h)      # (last: it counts conv2's call under conv3x3, and the declined path asks it again)
         if not ok:
@@ -428,6 +462,90 @@ def _geglu_forward(self, x, *args, **kwargs):
     return a * F.gelu(gate)
 
 
+# ---- the up blocks without torch.cat([x, skip], 1) -----------------------------------------------------------------------------------------
+# class name -> the parameters of its forward, in order: the stand-in's UpBlock, diffusers 0.10.0's UpBlock2D and CrossAttnUpBlock2D
+_UP_BLOCKS = {
+    "UpBlock": ("x", "skips", "temb", "ctx"),
+    "UpBlock2D": ("hidden_states", "res_hidden_states_tuple", "temb", "upsample_size"),
+    "CrossAttnUpBlock2D": ("hidden_states", "res_hidden_states_tuple", "temb", "encoder_hidden_states", "upsample_size"),
+}
+
+
+def _no_hooks(m):
+    return not m._forward_hooks and not m._forward_pre_hooks and not nn.modules.module._global_forward_hooks and not nn.modules.module._global_forward_pre_hooks
+
+
+def _resnet_cat(res, x1, x2, temb):
+    """`res(torch.cat([x1, x2], 1), temb)` of an up block. Where the block is plug-covered and BOTH readers of the concatenation take it in
+    two parts -- norm1 (ops.group_norm_cat) and conv2 + shortcut (ops.conv3x3_shortcut_cat, asked inside the body once conv2's input
+    exists) -- the tensor is never made; every other case materialises it and calls the block exactly as the stock up block does.
+    Counted under `concat` either way (not rated)."""
+    own = res.__dict__.get("forward")
+    shortcut = getattr(res, "conv_shortcut", None)
+    ok = (CONCAT and CONV_SHORTCUT and FUSED_NORM and getattr(own, "__func__", None) is _resnet_forward and _no_hooks(res)
+          and torch.is_tensor(x1) and torch.is_tensor(x2) and x1.dtype == x2.dtype and not torch.is_autocast_enabled()
+          and not (torch.is_grad_enabled() and (x1.requires_grad or x2.requires_grad))
+          and (temb is None or torch.is_tensor(temb))
+          and shortcut is not None and _is_conv1x1(shortcut) and shortcut.bias is not None and getattr(res, "output_scale_factor", 1.0) == 1.0
+          and x1.dim() == 4 and x2.dim() == 4 and x1.shape[1] % 64 == 0 and x2.shape[1] % 64 == 0
+          and x1.shape[1] + x2.shape[1] == res.norm1.num_channels == shortcut.in_channels
+          and res.norm1.weight is not None and res.norm1.weight.dtype == x1.dtype
+          and not (torch.is_grad_enabled() and res.norm1.weight.requires_grad)
+          and FOLD_CONV_BIAS and _plain_conv(res.conv1) and _plain_conv(res.conv2) and res.conv1.bias.dtype == x1.dtype
+          and _is_conv3x3(res.conv2) and res.conv2.stride == (1, 1) and res.conv2.weight.dtype == x1.dtype
+          and res.conv2.in_channels % 64 == 0 and res.conv2.out_channels % 64 == 0
+          and x1.shape[0] * x1.shape[2] * x1.shape[3] < STOCK_FROM_ROWS
+          and ops.group_norm_cat_takes(x1, x2, res.norm1.num_groups, res.norm1.weight, res.norm1.bias))
+    if ok:
+        return _resnet_body(res, None, temb, pair=(x1, x2))
+    _STATS["concat"][1] += 1
+    return res(torch.cat([x1, x2], dim=1), temb)
+
+
+def _up_block_covered(m):
+    res, att, ups = getattr(m, "resnets", None), getattr(m, "attentions", None), getattr(m, "upsamplers", None)
+    return (m.__class__.__name__ in _UP_BLOCKS and isinstance(res, nn.ModuleList) and len(res) > 0
+            and (att is None or (isinstance(att, nn.ModuleList) and len(att) == len(res))) and (ups is None or isinstance(ups, nn.ModuleList))
+            and (m.__class__.__name__ != "CrossAttnUpBlock2D" or att is not None))
+
+
+def _up_block_forward(self, *args, **kwargs):
+    """The forward of an up block restated without the concatenation: the stand-in's ``UpBlock.forward(x, skips, temb, ctx)`` and diffusers
+    0.10.0's ``UpBlock2D.forward(hidden_states, res_hidden_states_tuple, temb=None, upsample_size=None)`` /
+    ``CrossAttnUpBlock2D.forward(hidden_states, res_hidden_states_tuple, temb=None, encoder_hidden_states=None, upsample_size=None)``::
+
+        for resnet (, attn): hidden = resnet(cat([hidden, skips.pop()], 1), temb) (; hidden = attn(hidden, context)); upsamplers; return
+
+    with each ``resnet(cat(...))`` handed to `_resnet_cat` as the pair. Any call this restatement does not know (other keywords, more
+    positionals, gradient checkpointing while training, hooks on the block, fewer skips than resnets), and every call with PWW_CONCAT=0,
+    reaches the module's own forward with its arguments untouched."""
+    names = _UP_BLOCKS[self.__class__.__name__]
+    standin = self.__class__.__name__ == "UpBlock"
+    vals = dict(zip(names, args))
+    known = CONCAT and len(args) <= len(names) and all(k in names and k not in vals for k in kwargs) and _no_hooks(self)
+    if known:
+        vals.update(kwargs)
+        skips = vals.get(names[1])
+        known = (names[0] in vals and isinstance(skips, (tuple, list)) and len(skips) >= len(self.resnets) and (not standin or len(vals) == len(names))
+                 and not (self.training and getattr(self, "gradient_checkpointing", False)))
+    if not known:
+        return self._pww_orig_forward(*args, **kwargs)
+    x, temb = vals[names[0]], vals.get("temb")
+    attentions, upsamplers = getattr(self, "attentions", None), getattr(self, "upsamplers", None)
+    for i, res in enumerate(self.resnets):
+        x = _resnet_cat(res, x, skips[-1], temb)
+        skips = skips[:-1]
+        if attentions is not None:
+            x = attentions[i](x, vals["ctx"]) if standin else attentions[i](x, encoder_hidden_states=vals.get("encoder_hidden_states")).sample
+    if upsamplers is not None:
+        if standin:
+            x = upsamplers[0](x)
+        else:
+            for up in upsamplers:
+                x = up(x, vals.get("upsample_size"))
+    return (x, skips) if standin else x
+
+
 def install_blocks(unet):
     """Put the fused norms under every ``ResnetBlock2D`` and every other ``nn.GroupNorm`` of `unet`. Returns (resnets, norms) patched."""
     n_res = n_gn = 0
@@ -459,6 +577,8 @@ def install_blocks(unet):
             owned.add(id(_upsample_conv(m)))
         elif _is_conv3x3(m) and id(m) not in owned:
             fwd = _conv3x3_forward
+        elif name in _UP_BLOCKS and _up_block_covered(m):
+            fwd = _up_block_forward
         if fwd is not None and "_pww_orig_forward" not in m.__dict__:
             m.__dict__["_pww_orig_forward"] = m.forward
             m.forward = types.MethodType(fwd, m)

@@ -1206,6 +1206,101 @@ def conv3x3_shortcut(h, conv2_weight, conv2_bias, x, shortcut_weight, shortcut_b
     return y
 
 
+# ---- the two readers of torch.cat([x1, x2], 1) in an up block, reading the halves where they lie (csrc/pww_concat.hip, libpww_hip_concat.so)
+def _cat_pair(x1, x2, grid):
+    """Two channels_last 4-d float16 / bfloat16 tensors of one dtype, device, batch and size on a HIP device, 16-byte aligned, their channel
+    counts multiples of `grid`: what both two-source kernels ask of the pair."""
+    if not (torch.is_tensor(x1) and torch.is_tensor(x2) and x1.is_cuda and x1.device == x2.device and x1.dim() == 4 and x2.dim() == 4
+            and x1.dtype in _DT and x2.dtype == x1.dtype):
+        return False
+    (B, C1, H, W), C2 = x1.shape, x2.shape[1]
+    return ((x2.shape[0], x2.shape[2], x2.shape[3]) == (B, H, W) and C1 % grid == 0 and C2 % grid == 0 and C1 > 0 and C2 > 0
+            and x1.is_contiguous(memory_format=torch.channels_last) and x2.is_contiguous(memory_format=torch.channels_last)
+            and x1.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0)
+
+
+def _gn_cat_desc(x1, x2, num_groups, eps, act):
+    B, C1, H, W = x1.shape
+    return _lib.ConcatGnDesc(ctypes.sizeof(_lib.ConcatGnDesc), _DT[x1.dtype], B, C1, x2.shape[1], H * W, int(num_groups), float(eps),
+                             _lib.ACT_SILU if act == "silu" else _lib.ACT_NONE, 0)
+
+
+def group_norm_cat_takes(x1, x2, num_groups, weight=None, bias=None):
+    """True when pww_concat_group_norm_fwd runs this call: a pair as `_cat_pair` describes it with channel counts on the 8 grid, affine
+    parameters of its dtype (or none), a shape group_norm takes for C1 + C2 channels in channels_last, and the side library there."""
+    if not _cat_pair(x1, x2, 8):
+        return False
+    C = x1.shape[1] + x2.shape[1]
+    for t in (weight, bias):
+        if t is not None and not (torch.is_tensor(t) and t.dtype == x1.dtype and tuple(t.shape) == (C,) and t.device == x1.device):
+            return False
+    lib = _lib.load_concat()
+    return lib is not None and int(lib.pww_concat_group_norm_workspace_bytes(ctypes.byref(_gn_cat_desc(x1, x2, num_groups, 1e-5, None)))) > 0
+
+
+def group_norm_cat(x1, x2, num_groups, weight=None, bias=None, eps=1e-5, act=None, workspace=None):
+    """group_norm(torch.cat([x1, x2], 1), ...) for two channels_last tensors without the concatenation: the same launch form, summation
+    order and roundings, so the same bits. The output is a channels_last [B, C1 + C2, H, W]. act None | "silu"."""
+    _require_gpu(x1, x2)
+    if act not in (None, "silu"):
+        raise PwwHipError("group_norm_cat: act must be None or 'silu'")
+    if not group_norm_cat_takes(x1, x2, num_groups, weight, bias):
+        raise PwwHipError("group_norm_cat: needs two channels_last float16/bfloat16 tensors of one dtype, batch and size with channel counts multiples "
+                          "of 8, C1 + C2 a shape group_norm takes, and libpww_hip_concat.so %s" % _lib._HINT)
+    B, C1, H, W = x1.shape
+    weight = weight.contiguous() if weight is not None else None
+    bias = bias.contiguous() if bias is not None else None
+    d = _gn_cat_desc(x1, x2, num_groups, eps, act)
+    lib = _lib.load_concat()
+    need = int(lib.pww_concat_group_norm_workspace_bytes(ctypes.byref(d)))
+    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=x1.device)
+    out = torch.empty((B, C1 + x2.shape[1], H, W), dtype=x1.dtype, device=x1.device, memory_format=torch.channels_last)
+    with torch.cuda.device(x1.device):
+        _lib.check(lib.pww_concat_group_norm_fwd(_ptr(x1), _ptr(x2), _ptr(weight), _ptr(bias), _ptr(out), ctypes.byref(d), _ptr(ws), ws.numel(), _stream()),
+                   "pww_concat_group_norm_fwd", lib)
+    return out
+
+
+def conv3x3_shortcut_cat_takes(h, conv2_weight, x1, x2, shortcut_weight):
+    """True when pww_concat_convtail_fwd runs this call: what conv3x3_shortcut_takes asks of (h, conv2_weight, torch.cat([x1, x2], 1),
+    shortcut_weight), with both parts on the 64-channel grid, and the side library there."""
+    if not (conv3x3_takes(h, conv2_weight) and _cat_pair(x1, x2, 64) and x1.device == h.device and x1.dtype == h.dtype
+            and torch.is_tensor(shortcut_weight) and shortcut_weight.dtype == h.dtype and shortcut_weight.device == h.device):
+        return False
+    w2 = _linear_weight(shortcut_weight)
+    B, C1, H, W = x1.shape
+    Ct = C1 + x2.shape[1]
+    return (w2 is not None and tuple(w2.shape) == (conv2_weight.shape[0], Ct) and (B, H, W) == (h.shape[0], h.shape[2], h.shape[3])
+            and B * H * W * Ct < 2 ** 31 // 4 and _lib.load_concat() is not None)
+
+
+def conv3x3_shortcut_cat(h, conv2_weight, conv2_bias, x1, x2, shortcut_weight, shortcut_bias, tile_n=0, splitk=0):
+    """conv3x3_shortcut(h, conv2_weight, conv2_bias, torch.cat([x1, x2], 1), shortcut_weight, shortcut_bias) without the concatenation: the
+    same tile, K order, split and epilogue, so the same bits. tile_n / splitk: 0 = the choice conv3x3_shortcut makes."""
+    _require_gpu(h, conv2_weight, conv2_bias, x1, x2, shortcut_weight, shortcut_bias)
+    if not conv3x3_shortcut_cat_takes(h, conv2_weight, x1, x2, shortcut_weight):
+        raise PwwHipError("conv3x3_shortcut_cat: needs channels_last float16/bfloat16 h, x1 and x2 of one dtype, batch and size, channel counts multiples "
+                          "of 64, a 3 x 3 weight and a dense 1 x 1 weight of that dtype over C1 + C2 channels, and libpww_hip_concat.so %s" % _lib._HINT)
+    B, C, H, W = h.shape
+    Cout = conv2_weight.shape[0]
+    w = _khwc_weight(conv2_weight)
+    w2 = _linear_weight(shortcut_weight)
+    biases = []
+    for name, b in (("conv2_bias", conv2_bias), ("shortcut_bias", shortcut_bias)):
+        if not torch.is_tensor(b) or b.dtype != h.dtype or tuple(b.shape) != (Cout,):
+            raise PwwHipError("conv3x3_shortcut_cat: %s must be a %s [%d]" % (name, h.dtype, Cout))
+        biases.append(b.contiguous() if b.data_ptr() % 8 == 0 else b.clone(memory_format=torch.contiguous_format))
+    lib = _lib.load_concat()
+    d = _lib.ConcatTailDesc(ctypes.sizeof(_lib.ConcatTailDesc), _DT[h.dtype], B, H, W, C, x1.shape[1], x2.shape[1], Cout, int(tile_n), int(splitk), 0)
+    y = torch.empty((B, Cout, H, W), dtype=h.dtype, device=h.device, memory_format=torch.channels_last)
+    nbytes = int(lib.pww_concat_convtail_workspace_bytes(ctypes.byref(d)))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=h.device) if nbytes else None
+    with torch.cuda.device(h.device):
+        _lib.check(lib.pww_concat_convtail_fwd(_ptr(h), _ptr(w), _ptr(x1), _ptr(x2), _ptr(w2), _ptr(biases[0]), _ptr(biases[1]), _ptr(y), ctypes.byref(d),
+                                               _ptr(ws), nbytes, _stream()), "pww_concat_convtail_fwd", lib)
+    return y
+
+
 # ---- linear layers with the post-processing of the GEMM's output in its epilogue (csrc/pww_linear.hip, libpww_hip_linear.so) ------------
 def _linear_weight(weight):
     """[N, K] view of an nn.Linear weight or of a 1 x 1 conv weight ([N, K, 1, 1]), in place; None when it is neither or not dense."""
