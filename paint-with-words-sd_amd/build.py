@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Ten libraries come out of the same sources:
+Eleven libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
                               measured and not made a default (include/pww_hip.h, section "experiments"). Built by the tests / tools that
@@ -23,6 +23,7 @@ Ten libraries come out of the same sources:
                               and SIDE_LIBS_EXTRA, the open-ended home of every later side library:
                                 canvas    canvases larger than the UNet's window: the gather of the windows and the combine of their noise predictions
                                 concat    the up blocks without torch.cat: GroupNorm and conv2 + shortcut reading the two halves of the concatenation in place
+                                hold      region strength: the strength map of an img2img request, its feather, and the per-step hold of the pixels not yet released
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -63,6 +64,7 @@ SIDE_LIBS_CONV = {
 SIDE_LIBS_EXTRA = {
     "canvas": ("pww_canvas.hip", [], "canvases larger than the UNet's window: the windows' gather and the combine of their noise predictions"),
     "concat": ("pww_concat.hip", [], "the up blocks without torch.cat: GroupNorm and conv2 + shortcut over the two halves of the concatenation"),
+    "hold": ("pww_hold.hip", [], "region strength: the strength map, its feather and the per-step hold of the pixels not yet released"),
 }
 ALL_SIDE_LIBS = {**SIDE_LIBS, **SIDE_LIBS_CONV, **SIDE_LIBS_EXTRA}
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
@@ -74,6 +76,7 @@ LONG_UNITS, SCOPE_UNITS, LINEAR_UNITS, REGIONS_UNITS, LORA_UNITS = (SIDE_UNITS[n
 LIB_CONVTAIL, CONVTAIL_UNITS = SIDE_PATHS["convtail"], SIDE_UNITS["convtail"]
 LIB_CANVAS, CANVAS_UNITS = SIDE_PATHS["canvas"], SIDE_UNITS["canvas"]
 LIB_CONCAT, CONCAT_UNITS = SIDE_PATHS["concat"], SIDE_UNITS["concat"]
+LIB_HOLD, HOLD_UNITS = SIDE_PATHS["hold"], SIDE_UNITS["hold"]
 SIDE_PUBLIC_HEADERS = {"canvas": ["pww_hip_regions.h"]}       # include/ headers a side library's own header includes (besides pww_hip.h)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
@@ -83,8 +86,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
          "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
-# pww_mask.hip, pww_regions.hip and pww_canvas.hip restate fp32 formulas that must match a CPU restatement bit for bit: no FMA contraction.
-PER_FILE_FLAGS = {"pww_mask.hip": ["-ffp-contract=off"], "pww_regions.hip": ["-ffp-contract=off"], "pww_canvas.hip": ["-ffp-contract=off"]}
+# pww_mask.hip, pww_regions.hip, pww_canvas.hip and pww_hold.hip restate fp32 formulas that must match a CPU restatement bit for bit: no FMA contraction.
+PER_FILE_FLAGS = {"pww_mask.hip": ["-ffp-contract=off"], "pww_regions.hip": ["-ffp-contract=off"], "pww_canvas.hip": ["-ffp-contract=off"],
+                  "pww_hold.hip": ["-ffp-contract=off"]}
 
 
 def _newer(target, deps):
@@ -160,6 +164,7 @@ def build_lora(force=False, verbose=False): return build_side("lora", force, ver
 def build_convtail(force=False, verbose=False): return build_side("convtail", force, verbose)  # noqa: E704
 def build_canvas(force=False, verbose=False): return build_side("canvas", force, verbose)  # noqa: E704
 def build_concat(force=False, verbose=False): return build_side("concat", force, verbose)  # noqa: E704
+def build_hold(force=False, verbose=False): return build_side("hold", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):

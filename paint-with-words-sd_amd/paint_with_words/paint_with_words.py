@@ -22,10 +22,10 @@ from PIL import Image
 import pww_hip
 from pww_hip.attention import inj_forward  # noqa: F401  (same import path as the reference's symbol)
 from pww_hip.conditioning import check_prompt_chunks, prompt_chunk_count, check_negative_context
-from pww_hip.conditioning import check_region_prompts, check_loras, region_entries, encode_region_prompts
+from pww_hip.conditioning import check_region_prompts, check_loras, region_entries, encode_region_prompts, check_region_strength
 from pww_hip.conditioning import (always_round, _extract_seed_and_sigma_from_context, _encode_text_color_inputs,  # noqa: F401
                                   _get_binary_mask, gaussian_blur_mask)
-from pww_hip.sampler import PwWSampler, initial_latents, canvas_plan
+from pww_hip.sampler import PwWSampler, initial_latents, canvas_plan, hold_first
 
 try:  # the reference's dependency; absent in the offline build image
     from diffusers import AutoencoderKL, LMSDiscreteScheduler, UNet2DConditionModel
@@ -214,16 +214,82 @@ def _seeded_noise(tools, device, seeds, timesteps, seeds_info, sizes):
     return torch.cat(lats, dim=0).to(device) * scheduler.init_noise_sigma, None
 
 
-def _noised_images(tools, device, seeds, timesteps, seeds_info, init_images):
-    """img2img (:459-468): the init images through the VAE encoder, noised to the first timestep (noise from the global generator)."""
+def _held_images(tools, device, seeds, timesteps, seeds_info, init_images, made_of=True):
+    """img2img (:459-468): the init images through the VAE encoder, noised to the first timestep (noise from the global generator) -- and what
+    they were made of: -> (latents, None, the encoded init latents x0, the noise z), the last two for a request with region strengths
+    (made_of=False: not formed)."""
     vae, scheduler = tools[0], tools[4]
-    lats = []
+    lats, inits, noises = [], [], []
     for init_image in init_images:
         image = preprocess(init_image).to(device=device)
         init_latents = 0.18215 * vae.encode(image.to(vae.dtype)).latent_dist.sample().float()
         noise = torch.randn(init_latents.shape).to(device)
         lats.append(scheduler.add_noise(init_latents, noise, timesteps[:1]))
-    return torch.cat(lats, dim=0), None
+        inits.append(init_latents), noises.append(noise)
+    if not made_of:
+        return torch.cat(lats, dim=0), None
+    return torch.cat(lats, dim=0), None, torch.cat(inits, dim=0), torch.cat(noises, dim=0)
+
+
+def _noised_images(tools, device, seeds, timesteps, seeds_info, init_images):
+    """img2img (:459-468): the init images through the VAE encoder, noised to the first timestep (noise from the global generator)."""
+    return _held_images(tools, device, seeds, timesteps, seeds_info, init_images, made_of=False)
+
+
+def _hold_request(entries, feather, strength, num_inference_steps, color_map_images, init_images):
+    """The region strengths of a call (check_region_strength's entries, one list or None per request; None: the feature is off -> None)
+    against what else the call was given, before any model is touched -> the `hold` argument of _generate: {"entries", "feather", "base":
+    `strength`, the strength of every pixel whose colour is not named, "steps": T, "first": i0, the first step of the T-step schedule the
+    request runs: the step that releases the largest strength any request names (sampler.hold_first), whether or not the colour occurs in
+    a map}. ValueError: a base strength outside [0, 1], a call whose largest strength releases nothing in T steps, a color map that is not
+    8 x the latent the init image encodes to (its size at the next lower multiple of 32)."""
+    if entries is None:
+        return None
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 <= float(strength) <= 1.0:      # (a NaN fails the comparison)
+        raise ValueError("region_strength: `strength`, the strength of every pixel whose colour is not named, must be a number in [0, 1] (got %r)" % (strength,))
+    if isinstance(num_inference_steps, bool) or not isinstance(num_inference_steps, int) or num_inference_steps < 1:
+        raise ValueError("region_strength: num_inference_steps must be a positive integer (got %r)" % (num_inference_steps,))
+    for color_map, init_image in zip(color_map_images, init_images):
+        if color_map is None:
+            raise ValueError("region_strength needs a color map")
+        latent = tuple(side - side % 32 for side in init_image.size)
+        if tuple(color_map.size) != latent:
+            raise ValueError("region_strength: the color map is %d x %d but the init image encodes to a latent of %d x %d pixels / 8: the color map must "
+                             "be 8 x the latent on both axes" % (tuple(color_map.size) + latent))
+    top = max([float(strength)] + [s for e in entries if e is not None for _, s in e])
+    first = hold_first(num_inference_steps, top)
+    if first >= num_inference_steps:
+        raise ValueError("region_strength: the largest strength of the call (%g) releases no pixel in %d steps: nothing would be denoised"
+                         % (top, num_inference_steps))
+    return {"entries": entries, "feather": float(feather), "base": float(strength), "steps": num_inference_steps, "first": first}
+
+
+def _hold_scheduler_check(scheduler):
+    """Region strengths count the steps of the schedule from its start and noise the init latent per step: a scheduler that shifts its
+    timesteps (`steps_offset`) or cannot add noise is refused, before the conditioning is formed."""
+    config = getattr(scheduler, "config", None)
+    offset = (config.get("steps_offset", 0) if hasattr(config, "get") else getattr(config, "steps_offset", 0)) or 0
+    if offset != 0:
+        raise ValueError("region_strength: a scheduler with steps_offset = %r is not supported (%s)" % (offset, type(scheduler).__name__))
+    if not hasattr(scheduler, "add_noise"):
+        raise ValueError("region_strength needs a scheduler with add_noise (%s has none)" % type(scheduler).__name__)
+
+
+def _strength_maps(hold, color_map_images, device):
+    """S, fp32 [n, h, w]: the strength map of every request from its color map (ops.hold_strength_map: one launch, two more with a feather);
+    a request that names no colour has the base strength everywhere. Requests that share a map and a dict share the launches."""
+    made, out = {}, []
+    for color_map, entries in zip(color_map_images, hold["entries"]):
+        key = (id(color_map), id(entries))
+        if key not in made:
+            if entries is None:
+                width, height = color_map.size
+                made[key] = torch.full((height // 8, width // 8), float(np.float32(hold["base"])), dtype=torch.float32, device=device)
+            else:
+                rgb = torch.as_tensor(np.ascontiguousarray(np.array(color_map.convert("RGB"))), dtype=torch.uint8).to(device)
+                made[key] = pww_hip.ops.hold_strength_map(rgb, [e[0] for e in entries], [e[1] for e in entries], hold["base"], hold["feather"])
+        out.append(made[key])
+    return torch.stack(out, dim=0)
 
 
 def _txt2img_or_img2img(sizes, init_images, strength):
@@ -236,7 +302,7 @@ def _txt2img_or_img2img(sizes, init_images, strength):
 def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
               unconditional_input_prompt, start, strength=None, map_sizes=None, on_step=None, use_region_sigma=True, shared=False,
               max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0, region_prompts=None, region_base_weight=0.0,
-              region_feather=0.0, loras=None, canvas=None):
+              region_feather=0.0, loras=None, canvas=None, hold=None):
     """The body behind every face of the package (reference :414-506, paint_with_words_inpaint.py:160-262): conditioning per request (once
     if `shared`: every request has the same map, context and prompt), the timesteps, the initial state, one denoise loop over all images.
     Returns the final latents [n, 4, h, w].
@@ -247,9 +313,13 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
     regions of the unconditional prompt (see paint_with_words). region_prompts: None, or one dict per request (_region_requests) -- a full
     prompt per colour, blended per latent pixel where guidance is combined (see paint_with_words). loras: None, or what check_loras made of the
     `lora` / `region_loras` keywords. canvas: None, or the plan of ONE request whose color map is larger than the UNet's window
-    (_canvas_request): the conditioning is formed per window on the crop of the map, the initial state at canvas size."""
+    (_canvas_request): the conditioning is formed per window on the crop of the map, the initial state at canvas size. hold: None, or the
+    region strengths of an img2img call (_hold_request): `start` is then _held_images, the request runs the schedule from hold["first"], and
+    the sampler is handed the init latents, the noise and one strength map per request (at canvas size for a canvas request)."""
     unet, text_encoder, tokenizer, scheduler = tools[1:]
     n = len(seeds)
+    if hold is not None:
+        _hold_scheduler_check(scheduler)
     sampler = _sampler_for(unet, scheduler)   # also installs the attention plug
     conds, unconds, seeds_info = [], [], []
     region_texts = [e[1] for r in (region_prompts or []) for e in region_entries(r)]
@@ -287,13 +357,19 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
 
     scheduler.set_timesteps(num_inference_steps)
     timesteps = scheduler.timesteps
-    if strength is not None:
+    if hold is not None:
+        timesteps = timesteps[hold["first"]:]
+    elif strength is not None:
         offset = scheduler.config.get("steps_offset", 0)
         init_timestep = min(int(num_inference_steps * strength) + offset, num_inference_steps)
         timesteps = timesteps[max(num_inference_steps - init_timestep + offset, 0):]
 
-    latents, extra_channels = start(tools, device, seeds, timesteps, seeds_info)
+    latents, extra_channels, *made_of = start(tools, device, seeds, timesteps, seeds_info)
     more = {} if regions is None else {"regions": regions}        # (a call without region prompts is, argument for argument, the call of before)
+    if hold is not None:
+        # (the VAE's convolution may hand its output back in channels_last memory: the hold launch reads NCHW)
+        more["hold"] = {"init": made_of[0].contiguous(), "noise": made_of[1].contiguous(), "strength": _strength_maps(hold, color_map_images, device), "steps": hold["steps"],
+                        "first": hold["first"]}
     if canvas is not None:
         more["canvas"] = canvas
     if loras is not None:
@@ -339,6 +415,8 @@ def paint_with_words(
     return_latents: bool = False,
     negative_color_context: Optional[Dict[Tuple[int, int, int], str]] = None,
     negative_strength: float = 1.0,
+    region_strength=None,
+    region_strength_feather: float = 0.0,
     lora=None,
     region_loras=None,
     canvas_window: Optional[int] = None,
@@ -381,20 +459,38 @@ def paint_with_words(
     The initial latent (with region seeds, against the whole map) and the img2img encoding are formed at canvas size. None (the default), or
     a map no larger than the window on both axes, is the plain call; a map smaller than the window on one axis, a side that is not a
     multiple of 8, more than 64 windows or a value out of range raise ValueError. record_attention_maps() is refused around such a call.
-    Not part of this: the *_batch forms, the inpaint function, both pipeline classes, windows spread over several GPUs, non-square windows."""
+    Not part of this: the *_batch forms, the inpaint function, both pipeline classes, windows spread over several GPUs, non-square windows.
+    `region_strength` / `region_strength_feather` (extension, img2img only; Differential Diffusion, Levin and Fried 2023): a denoising
+    strength per colour of the color map, {(r, g, b) | "#rrggbb": s} with s in [0, 1], 1 to 8 colours that need not appear in color_context
+    -- "repaint the lake hard, touch the sky lightly, leave the house alone" on a stock 4-channel UNet. `strength` stays the strength of
+    every pixel whose colour is not named. Per latent pixel S = strength + sum_k M_k (s_k - strength), M_k the share of the pixel's 8 x 8
+    block that has colour k, clamped to [0, 1] and feathered by a Gaussian of `region_strength_feather` latent pixels (at most 8). With T =
+    num_inference_steps a pixel is released at step g iff S >= (T - g) / T (in fp32; equality releases); the call runs the schedule from the
+    step that releases the largest strength it names -- whether or not that colour occurs in the map, so the step count does not depend on
+    the picture -- and after every scheduler step one launch puts the pixels the next step does not release back to the init latent noised to
+    that step's timestep (with the request's one noise tensor). Pixels that are never released come back as the encoded init latent, bit
+    for bit; if every named strength equals `strength` the result is the plain img2img call's. It composes with negative regions, region
+    prompts, LoRA adapters, long prompts and canvases (the strength map is then formed at canvas size). None / {} is the call without the
+    feature. ValueError: no init_image, a strength outside [0, 1], more than 8 colours, a colour named twice, a feather outside [0, 8], a
+    color map that is not 8 x the latent, strengths that release nothing in T steps, a scheduler with steps_offset or without add_noise."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context)
+    held = check_region_strength(region_strength, region_strength_feather, None if init_image is None else [init_image])
     loras = check_loras(lora, region_loras, region_prompts, tools=preloaded_utils)
     color_map_image.size     # the reference dereferences it unconditionally (:414): None raises here too
     canvas = _canvas_request(color_map_image.size, canvas_window, canvas_stride, canvas_ramp)
+    hold = _hold_request(held, region_strength_feather, strength, num_inference_steps, [color_map_image], [init_image])
     tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
     start, strength = _txt2img_or_img2img([color_map_image.size], None if init_image is None else [init_image], strength)
+    more = {} if canvas is None else {"canvas": canvas}
+    if hold is not None:      # (a call without region strengths is, argument for argument, the call of before)
+        start, more["hold"] = partial(_held_images, init_images=[init_image]), hold
     latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps, guidance_scale,
                         weight_function, unconditional_input_prompt, start, strength, shared=True, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=[negative_color_context], negative_strength=negative_strength,
                         region_prompts=_region_requests(region_prompts, 1), region_base_weight=region_base_weight, region_feather=region_feather,
-                        loras=loras, **({} if canvas is None else {"canvas": canvas}))
+                        loras=loras, **more)
     out = _finish(tools, latents, return_latents)
     return out if return_latents else out[0]
 
@@ -420,6 +516,8 @@ def paint_with_words_batch(
     return_latents: bool = False,
     negative_color_context: Union[None, Dict, Sequence[Optional[Dict]]] = None,
     negative_strength: float = 1.0,
+    region_strength=None,
+    region_strength_feather: float = 0.0,
     lora=None,
     region_loras=None,
     region_prompts=None,
@@ -438,12 +536,15 @@ def paint_with_words_batch(
     shared by every request or one (or None) per seed, like color_contexts. max_prompt_chunks: see paint_with_words; with per-image prompts
     every image is padded (with empty chunks) to the largest chunk count of the batch. region_prompts / region_base_weight / region_feather:
     see paint_with_words; one dict for all requests or one per seed, every request with the same number of regions. lora / region_loras: see
-    paint_with_words; `lora` serves every request, region_loras is one dict for all requests or one (or None) per seed."""
+    paint_with_words; `lora` serves every request, region_loras is one dict for all requests or one (or None) per seed. region_strength /
+    region_strength_feather: see paint_with_words; one dict for all requests or one (or None) per seed -- all requests run the same steps:
+    from the step that releases the largest strength any of them names."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     seeds = list(seeds)
     n = len(seeds)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context, n_requests=n)
+    held = check_region_strength(region_strength, region_strength_feather, init_images, n_requests=n)
     loras = check_loras(lora, region_loras, region_prompts, n_requests=n, tools=preloaded_utils)
     if n == 0:
         return []
@@ -453,12 +554,16 @@ def paint_with_words_batch(
     if len({m.size for m in maps}) != 1:
         raise ValueError("paint_with_words_batch: all color maps of one call must have the same size, got %s"
                          % sorted({m.size for m in maps}))
+    hold = _hold_request(held, region_strength_feather, strength, num_inference_steps, maps, inits or [])
     tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
     start, strength = _txt2img_or_img2img([m.size for m in maps], inits, strength)
+    more = {}
+    if hold is not None:      # (a call without region strengths is, argument for argument, the call of before)
+        start, more["hold"] = partial(_held_images, init_images=inits), hold
     latents = _generate(tools, device, ctxs, maps, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
                         unconditional_input_prompt, start, strength, shared=shared, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=negs, negative_strength=negative_strength, region_prompts=_region_requests(region_prompts, n),
-                        region_base_weight=region_base_weight, region_feather=region_feather, loras=loras)
+                        region_base_weight=region_base_weight, region_feather=region_feather, loras=loras, **more)
     for c in strip:
         _extract_seed_and_sigma_from_context(c)
     return _finish(tools, latents, return_latents)

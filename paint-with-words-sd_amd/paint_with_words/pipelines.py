@@ -25,7 +25,8 @@ from PIL import Image
 
 import pww_hip
 from .paint_with_words import (LMSDiscreteScheduler, _generate, _finish, _pil_from_latents, _txt2img_or_img2img, check_prompt_chunks,
-                               check_negative_context, check_region_prompts, check_loras, _region_requests)
+                               check_negative_context, check_region_prompts, check_loras, _region_requests, check_region_strength, _hold_request,
+                               _held_images)
 from .paint_with_words_inpaint import _inpaint_start
 
 _warned = set()
@@ -59,6 +60,11 @@ class PaintWithWord_StableDiffusionPipeline:
     # `("name", scale)`, `pipe.region_loras = {(r, g, b): "name"}` for the colours of `pipe.region_prompts`. Attributes for the same reason.
     lora = None
     region_loras = None
+    # extension: region strength (see paint_with_words), img2img only: `pipe.region_strength = {(r, g, b): s}` -- a denoising strength per
+    # colour of the call's color map, `eta` being the strength of every other pixel -- and `pipe.region_strength_feather`. Attributes for the
+    # same reason. The inpaint class does not take them.
+    region_strength = None
+    region_strength_feather = 0.0
 
     def __init__(self, vae, text_encoder, tokenizer, unet, scheduler=None, safety_checker=None, feature_extractor=None,
                  requires_safety_checker: bool = False):
@@ -129,7 +135,7 @@ class PaintWithWord_StableDiffusionPipeline:
         return prompt, height, width, negative_prompt or ""
 
     def _run(self, start, strength, prompt, color_map_image, color_context, weight_function, num_inference_steps, guidance_scale,
-             negative_prompt, seed, output_type, return_dict, callback, callback_steps, loras=None):
+             negative_prompt, seed, output_type, return_dict, callback, callback_steps, loras=None, hold=None):
         """One request through the generation body of the function API, returned as the diffusers pipeline returns it (:821-842). The
         reference calls `callback(i, t, latents)` every `callback_steps` steps (:815-816)."""
         on_step = None if callback is None else (lambda i, t, latents: callback(i, t, latents) if i % callback_steps == 0 else None)
@@ -138,7 +144,8 @@ class PaintWithWord_StableDiffusionPipeline:
                         weight_function, negative_prompt, start, strength, on_step=on_step, use_region_sigma=False, shared=True,
                         max_prompt_chunks=self.max_prompt_chunks, negative_color_contexts=[self.negative_color_context],
                         negative_strength=self.negative_strength, region_prompts=_region_requests(self.region_prompts, 1),
-                        region_base_weight=self.region_base_weight, region_feather=self.region_feather, loras=loras)
+                        region_base_weight=self.region_base_weight, region_feather=self.region_feather, loras=loras,
+                        **({} if hold is None else {"hold": hold}))
         images = _finish(tools, lat, decode=lambda vae, latents: _decode(vae, latents, output_type))
         return SimpleNamespace(images=images, nsfw_content_detected=False) if return_dict else (images, False)
 
@@ -167,11 +174,15 @@ class PaintWithWord_StableDiffusionPipeline:
     ):
         """reference :629-842 (same parameter list, order and defaults). Prompts longer than 75 tokens: `self.max_prompt_chunks`."""
         loras = self._check_extensions()
+        held = check_region_strength(self.region_strength, self.region_strength_feather, None if image is None else [image])
         prompt, height, width, negative_prompt = self._check_inputs(prompt, height, width, negative_prompt, num_images_per_prompt, generator,
                                                                     latents, callback_steps)
+        hold = _hold_request(held, self.region_strength_feather, eta, num_inference_steps, [color_map_image], [image])
         start, strength = _txt2img_or_img2img([(width, height)], None if image is None else [image], eta)
+        if hold is not None:
+            start = partial(_held_images, init_images=[image])
         return self._run(start, strength, prompt, color_map_image, color_context, weight_function, num_inference_steps, guidance_scale,
-                         negative_prompt, seed, output_type, return_dict, callback, callback_steps, loras=loras)
+                         negative_prompt, seed, output_type, return_dict, callback, callback_steps, loras=loras, hold=hold)
 
 
 class PaintWithWord_StableDiffusionInpaintPipeline(PaintWithWord_StableDiffusionPipeline):
@@ -202,6 +213,8 @@ class PaintWithWord_StableDiffusionInpaintPipeline(PaintWithWord_StableDiffusion
         """reference paint_with_words_inpaint.py:340-575 (same parameter list, order and defaults). Prompts longer than 75 tokens:
         `self.max_prompt_chunks`."""
         loras = self._check_extensions()
+        if self.region_strength or self.region_strength_feather:
+            raise ValueError("region_strength / region_strength_feather are not part of the inpaint pipeline (img2img only)")
         if image is None or mask_image is None:
             raise ValueError("`image` and `mask_image` are required for inpainting")
         prompt, height, width, negative_prompt = self._check_inputs(prompt, height, width, negative_prompt, num_images_per_prompt, generator,

@@ -32,6 +32,9 @@ CANVAS_LIB_PATH = os.environ.get("PWW_HIP_CANVAS_LIB", os.path.join(_HERE, "libp
 #   concat    the up blocks without torch.cat: GroupNorm and conv2 + shortcut reading the two halves of the concatenation where they lie
 #             (include/pww_hip_concat.h): ops.group_norm_cat, ops.conv3x3_shortcut_cat. Its spec is in SIDE_EXTRA below.
 CONCAT_LIB_PATH = os.environ.get("PWW_HIP_CONCAT_LIB", os.path.join(_HERE, "libpww_hip_concat.so"))
+#   hold      region strength (img2img): the strength map of a request, its feather and the per-step hold of the pixels that are not
+#             released yet (include/pww_hip_hold.h): ops.hold_strength_map, ops.hold_apply. Its spec is in SIDE_EXTRA below.
+HOLD_LIB_PATH = os.environ.get("PWW_HIP_HOLD_LIB", os.path.join(_HERE, "libpww_hip_hold.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -100,6 +103,13 @@ CANVAS_MAX_WINDOWS, CANVAS_MAX_RAMP, CANVAS_MIN_WINDOW, CANVAS_MAX_WINDOW = 64, 
 CONCAT_EXPORTS = ("pww_concat_version", "pww_concat_last_error", "pww_concat_group_norm_workspace_bytes", "pww_concat_group_norm_fwd",
                   "pww_concat_convtail_workspace_bytes", "pww_concat_convtail_fwd")
 CONCAT_MIN_VERSION = 100
+
+
+# every symbol include/pww_hip_hold.h declares for libpww_hip_hold.so
+HOLD_EXPORTS = ("pww_hold_version", "pww_hold_last_error", "pww_hold_strength_map", "pww_hold_feather", "pww_hold_apply", "pww_hold_taps",
+                "pww_hold_thresholds")
+HOLD_MIN_VERSION = 100
+HOLD_MAX_COLORS, HOLD_MAX_FEATHER, HOLD_MAX_RADIUS, HOLD_MAX_STEPS = 8, 8.0, 24, 100000      # PWW_HOLD_MAX_* of the header
 
 
 class AttnDesc(ctypes.Structure):
@@ -379,6 +389,12 @@ SIDE_EXTRA = {
         "pww_concat_group_norm_fwd": ([_vp, _vp, _vp, _vp, _vp, _P(ConcatGnDesc), _vp, _sz, _vp], _int),
         "pww_concat_convtail_workspace_bytes": ([_P(ConcatTailDesc)], _sz),
         "pww_concat_convtail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(ConcatTailDesc), _vp, _sz, _vp], _int)}),
+    "hold": dict(path="HOLD_LIB_PATH", exports=HOLD_EXPORTS, min_version=HOLD_MIN_VERSION, missing_ok=False, needs="region strengths (img2img) need it", sigs={
+        "pww_hold_strength_map": ([_vp, _P(ctypes.c_uint8), _P(_f32), _f32, _vp, _i32, _i32, _i32, _vp], _int),
+        "pww_hold_feather": ([_vp, _vp, _vp, _i32, _i32, _f32, _vp], _int),
+        "pww_hold_apply": ([_vp, _vp, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _i64, _vp], _int),
+        "pww_hold_taps": ([_f32, _P(_f32), _i32], _int),
+        "pww_hold_thresholds": ([_i32, _P(_f32)], _int)}),
 }
 _side = {}      # name -> loaded handle
 
@@ -463,6 +479,11 @@ def load_canvas():
 def load_concat():
     lib = _side.get("concat")
     return lib if lib is not None else load_side("concat")
+
+
+def load_hold():
+    lib = _side.get("hold")
+    return lib if lib is not None else load_side("hold")
 
 
 class experiments:

@@ -192,6 +192,56 @@ def check_region_prompts(region_prompts, region_base_weight=0.0, region_feather=
     return counts[0] if counts else 0
 
 
+MAX_REGION_STRENGTHS = 8             # named colours per request (PWW_HOLD_MAX_COLORS of include/pww_hip_hold.h)
+MAX_REGION_STRENGTH_FEATHER = 8.0    # sigma of the feather of the strength map, in latent pixels (PWW_HOLD_MAX_FEATHER)
+
+
+def region_strength_entries(region_strength):
+    """One request's `region_strength` dict -> [((r, g, b), strength)], checked: 1 .. MAX_REGION_STRENGTHS entries {colour: strength}, the
+    colours in the grammar of region_prompts ((r, g, b) or "#rrggbb"), no colour twice, every strength a finite number in [0, 1]."""
+    if not isinstance(region_strength, dict):
+        raise ValueError("region_strength must be a dict {(r, g, b): strength} (got %r)" % type(region_strength).__name__)
+    if not 1 <= len(region_strength) <= MAX_REGION_STRENGTHS:
+        raise ValueError("region_strength takes 1 to %d colours (got %d)" % (MAX_REGION_STRENGTHS, len(region_strength)))
+    out = []
+    for color, value in region_strength.items():
+        try:
+            rgb = _rgb_of(color)
+        except ValueError as e:
+            raise ValueError(str(e).replace("region_prompts", "region_strength"))
+        if rgb in [e[0] for e in out]:
+            raise ValueError("region_strength names colour %s twice" % (rgb,))
+        s = _number(value, "region_strength[%s]" % (rgb,))
+        if not 0.0 <= s <= 1.0:
+            raise ValueError("region_strength[%s] must be in [0, 1] (got %r)" % (rgb, value))
+        out.append((rgb, s))
+    return out
+
+
+def check_region_strength(region_strength, feather=0.0, init_images=None, n_requests=None):
+    """The `region_strength` / `region_strength_feather` keywords of the entry points, checked before any model is touched.
+    region_strength: None or {} (off), one dict (region_strength_entries), or -- the batch forms, `n_requests` given -- a sequence with one
+    dict (or None / {}) per request. feather: a finite number of latent pixels in [0, MAX_REGION_STRENGTH_FEATHER]. Both need an init image
+    (`init_images`: whatever the face was given, None when it was given none): a strength per colour says how far a region moves from it.
+    -> None when the feature is off, else [per request: [((r, g, b), strength)] or None]."""
+    sigma = _number(feather, "region_strength_feather")
+    if not 0.0 <= sigma <= MAX_REGION_STRENGTH_FEATHER:
+        raise ValueError("region_strength_feather must be in [0, %g] latent pixels (got %r)" % (MAX_REGION_STRENGTH_FEATHER, feather))
+    if isinstance(region_strength, (list, tuple)):
+        if n_requests is None:
+            raise ValueError("region_strength must be a dict (a sequence of dicts is the batch form)")
+        if len(region_strength) != n_requests:
+            raise ValueError("region_strength has %d entries for %d requests" % (len(region_strength), n_requests))
+        per = list(region_strength)
+    else:
+        per = [region_strength] * (1 if n_requests is None else n_requests)
+    entries = [None if r is None or (isinstance(r, dict) and not r) else region_strength_entries(r) for r in per]
+    on = any(e is not None for e in entries)
+    if init_images is None and (on or sigma != 0.0):
+        raise ValueError("region_strength and region_strength_feather need an init image (img2img): the strength says how far a region moves from it")
+    return entries if on else None
+
+
 def check_loras(lora, region_loras, region_prompts=None, n_requests=None, tools=None):
     """The `lora` / `region_loras` keywords of the entry points, checked before any model is touched.
     lora: None, "name" or ("name", scale) -- the adapter of every row without one of its own (the conditional / base row, the unconditional

@@ -964,6 +964,75 @@ def canvas_combine(eps, ys, xs, canvas_hw, guidance_scale, ramp=0, masks=None, w
     return out
 
 
+# ---- region strength (libpww_hip_hold.so, include/pww_hip_hold.h) ---------------------------------------------------------------------
+def hold_strength_map(rgb, colors, strengths, s0, feather=0.0):
+    """uint8 colour map [H, W, 3] (device) + K (r, g, b) colours with their strengths + the base strength s0 -> fp32 [H // 8, W // 8]: per
+    latent pixel S = ((s0 + m_1 d_1) + m_2 d_2) + ..., m_k the share of its 8 x 8 pixel block that has colour k exactly and d_k =
+    fp32(s_k) - fp32(s0) (one fp32 subtraction, formed here), clamped to [0, 1]; feathered by a Gaussian of sigma `feather` latent pixels if
+    that is > 0 (two more launches, no limit on the plane)."""
+    import numpy as np
+    _require_gpu(rgb)
+    if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise PwwHipError("hold_strength_map needs a uint8 colour map [H, W, 3]")
+    rgb = rgb.contiguous()
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    K = len(colors)
+    flat = [int(v) for c in colors for v in c]
+    if len(flat) != 3 * K or any(not 0 <= v <= 255 for v in flat):
+        raise PwwHipError("hold_strength_map needs (r, g, b) colours of 8-bit values")
+    if len(strengths) != K:
+        raise PwwHipError("hold_strength_map: %d strengths for %d colours" % (len(strengths), K))
+    base = np.float32(s0)
+    deltas = [float(np.float32(s) - base) for s in strengths]
+    host_c = (ctypes.c_uint8 * max(len(flat), 1))(*flat)
+    host_d = (ctypes.c_float * max(K, 1))(*deltas)
+    out = torch.empty((H // 8, W // 8), dtype=torch.float32, device=rgb.device)
+    lib = _lib.load_hold()
+    with torch.cuda.device(rgb.device):
+        _lib.check(lib.pww_hold_strength_map(_ptr(rgb), host_c, host_d, float(base), _ptr(out), H, W, K, _stream()), "pww_hold_strength_map", lib)
+        if float(feather) != 0.0:
+            tmp = torch.empty_like(out)
+            _lib.check(lib.pww_hold_feather(_ptr(out), _ptr(tmp), _ptr(out), H // 8, W // 8, float(feather), _stream()), "pww_hold_feather", lib)
+    return out
+
+
+def hold_feather(plane, sigma):
+    """A separable normalised Gaussian of `sigma` pixels over an fp32 plane [h, w] (device), along the rows and then along the columns, in
+    global memory (two launches); returns a new plane."""
+    _require_gpu(plane)
+    if plane.dtype != torch.float32 or plane.dim() != 2:
+        raise PwwHipError("hold_feather needs a float32 plane [h, w]")
+    plane = plane.contiguous()
+    tmp, out = torch.empty_like(plane), torch.empty_like(plane)
+    lib = _lib.load_hold()
+    with torch.cuda.device(plane.device):
+        _lib.check(lib.pww_hold_feather(_ptr(plane), _ptr(tmp), _ptr(out), int(plane.shape[0]), int(plane.shape[1]), float(sigma), _stream()),
+                   "pww_hold_feather", lib)
+    return out
+
+
+def hold_apply(x, x0, z, S, theta, a, b):
+    """The hold of one step, IN PLACE on x (and returns it): x = (S < theta) ? a x0 + b z : x, with x, x0, z fp32 [n, C, h, w] and S fp32
+    [n, h, w], all contiguous (views are taken as they lie: nothing is copied). A select: held pixels are overwritten whatever they held,
+    released pixels are not touched. One launch."""
+    _require_gpu(x, x0, z, S)
+    if any(t.dtype != torch.float32 for t in (x, x0, z, S)):
+        raise PwwHipError("hold_apply needs float32 tensors (got %s)" % [str(t.dtype) for t in (x, x0, z, S)])
+    if x.dim() < 2 or x0.shape != x.shape or z.shape != x.shape or tuple(S.shape) != (x.shape[0],) + tuple(x.shape[2:]):
+        raise PwwHipError("hold_apply: x %s does not go with x0 %s, z %s and S %s ([n, C, ...] three times and [n, ...])"
+                          % (tuple(x.shape), tuple(x0.shape), tuple(z.shape), tuple(S.shape)))
+    if not all(t.is_contiguous() for t in (x, x0, z, S)):
+        raise PwwHipError("hold_apply needs contiguous tensors (x is written in place)")
+    if len({t.device for t in (x, x0, z, S)}) != 1:
+        raise PwwHipError("hold_apply needs its tensors on one device")
+    n, C = int(x.shape[0]), int(x.shape[1])
+    hw = x[0, 0].numel()
+    lib = _lib.load_hold()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.pww_hold_apply(_ptr(x), _ptr(x0), _ptr(z), _ptr(S), float(theta), float(a), float(b), n, C, hw, _stream()), "pww_hold_apply", lib)
+    return x
+
+
 # ---- GroupNorm (+ per-(image, channel) addend, + SiLU) of the blocks that call the attention path ------------------------------------
 def group_norm(x, num_groups, weight=None, bias=None, eps=1e-5, add=None, act=None, workspace=None, out=None, pre_bias=None):
     """act(GroupNorm(x + add[:, :, None, None])) for a [B, C, H, W] float16 / bfloat16 tensor in NCHW-contiguous or channels_last memory

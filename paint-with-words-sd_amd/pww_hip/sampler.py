@@ -23,7 +23,11 @@ A canvas larger than the UNet's window (`canvas=`, MultiDiffusion) is denoised a
 evaluation -- one context dict, one region plan, one LoRA row per window -- around two launches per step: ops.canvas_gather forms the windows'
 rows from the fp32 canvas latent, ops.canvas_combine the canvas-sized noise prediction from the UNet's output, and one scheduler.step follows
 on the canvas.
+Region strength (`hold=`, img2img; Differential Diffusion): every latent pixel has a strength S in [0, 1] and is released to the loop at the
+step its strength allows (hold_thresholds); one launch behind every scheduler.step (ops.hold_apply, outside the captured graph) puts the
+pixels that the next step does not release back to the init latent noised to that step's timestep.
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -66,6 +70,29 @@ def canvas_plan(canvas_hw, window, stride, ramp=0):
     Hc, Wc = (int(v) for v in canvas_hw)
     return {"size": (Hc, Wc), "window": (int(window), int(window)), "ys": ops.canvas_windows(Hc, window, stride),
             "xs": ops.canvas_windows(Wc, window, stride), "ramp": int(ramp)}
+
+
+def hold_thresholds(T):
+    """theta_g = fp32((T - g) / T) for g = 0 .. T, the quotient formed in double: a pixel of strength S is released at step g of a T-step
+    schedule iff fp32(S) >= theta_g (equality releases). A list of T + 1 Python floats that are exact fp32 values (pww_hold_thresholds of
+    include/pww_hip_hold.h)."""
+    T = int(T)
+    if T < 1:
+        raise ValueError("hold_thresholds: %d steps" % T)
+    return [float(np.float32((T - g) / T)) for g in range(T + 1)]
+
+
+def hold_first(T, strength):
+    """first(s): the smallest step g of a T-step schedule with fp32(s) >= theta_g -- the step at which a pixel of that strength is released,
+    and, for the largest strength of a request, the first step the request runs. T when s is below every theta but theta_T = 0 (nothing
+    would be denoised)."""
+    s = np.float32(strength)
+    if not 0.0 <= s <= 1.0:
+        raise ValueError("hold_first: strength %r outside [0, 1]" % (strength,))
+    for g, theta in enumerate(hold_thresholds(T)):
+        if s >= np.float32(theta):
+            return g
+    raise AssertionError("theta_T is 0")
 
 
 def _as_list(x, n):
@@ -441,6 +468,39 @@ class PwWSampler:
             raise ValueError("canvas: the scheduler scales its input by %g at t = %s, which is neither 1 nor 1 / sqrt(sigma^2 + 1) = %g" % (probe, float(t), 1.0 / denom))
         return denom
 
+    def _hold_coefficients(self, t):
+        """(a, b) of scheduler.add_noise at timestep t -- add_noise(x0, z, t) = a x0 + b z -- as two fp32 numbers, asked with one-element
+        probes like _input_scale asks scale_model_input; a scheduler whose add_noise is not of that form is refused."""
+        sch = self.scheduler
+        tt = torch.as_tensor(t).reshape(1)
+        one, zero = torch.ones(1, dtype=torch.float32), torch.zeros(1, dtype=torch.float32)
+        a, b, ab = (float(sch.add_noise(u, v, tt).reshape(-1)[0]) for u, v in ((one, zero), (zero, one), (one, one)))
+        if not abs(ab - (a + b)) <= 1e-6:
+            raise ValueError("region strength: the scheduler's add_noise is not a x0 + b z at t = %s (add_noise(1, 0) = %g, add_noise(0, 1) = %g, "
+                             "add_noise(1, 1) = %g)" % (float(t), a, b, ab))
+        return a, b
+
+    def _hold_table(self, hold, latents, timesteps, extra_channels):
+        """The `hold` argument of sample() against the request -> one (theta, a, b) per step of `timesteps`: what the launch behind that
+        step's scheduler.step holds the latent to. The steps are g = first .. T - 1 of the T-step schedule; behind step g the pixels that
+        step g + 1 does not release (S < theta_{g + 1}) go back to add_noise(x0, z, t_{g + 1}); behind the last step the pixels that were
+        never released (S < theta_{T - 1}) become x0."""
+        if extra_channels is not None:
+            raise ValueError("region strength: extra UNet input channels (inpainting) are not supported")
+        if not hasattr(self.scheduler, "add_noise"):
+            raise ValueError("region strength needs a scheduler with add_noise (%s has none)" % type(self.scheduler).__name__)
+        T, first = int(hold["steps"]), int(hold["first"])
+        if not 0 <= first < T or len(timesteps) != T - first:
+            raise ValueError("region strength: %d timesteps do not go with the steps %d .. %d of a %d-step schedule" % (len(timesteps), first, T - 1, T))
+        x0, z, S = hold["init"], hold["noise"], hold["strength"]
+        if (latents.dtype != torch.float32 or any(t.dtype != torch.float32 or t.device != latents.device for t in (x0, z, S)) or x0.shape != latents.shape
+                or z.shape != latents.shape or tuple(S.shape) != (latents.shape[0],) + tuple(latents.shape[2:])):
+            raise ValueError("region strength: the latent is %s %s; the init latent %s, the noise %s and the strength map %s must be float32 on its "
+                             "device, two of its shape and one [n, h, w]" % (tuple(latents.shape), latents.dtype, tuple(x0.shape), tuple(z.shape), tuple(S.shape)))
+        theta = hold_thresholds(T)
+        table = [(theta[first + i + 1],) + self._hold_coefficients(timesteps[i + 1]) for i in range(T - first - 1)]
+        return table + [(theta[T - 1], 1.0, 0.0)]
+
     def _canvas_check(self, canvas, latents, extra_channels):
         """The plan of a canvas request against its latent -> (n_w, (h, w)). The origins themselves are checked by the library."""
         if extra_channels is not None:
@@ -467,7 +527,7 @@ class PwWSampler:
 
     @torch.no_grad()
     def sample(self, cond, uncond, latents, timesteps, guidance_scale, weight_function, extra_channels=None,
-               on_step=None, negative_strength=1.0, regions=None, lora_rows=None, canvas=None):
+               on_step=None, negative_strength=1.0, regions=None, lora_rows=None, canvas=None, hold=None):
         """cond / uncond: the two context dicts of the PwW protocol, or one dict per image (per-image prompts / maps).
         regions: None, or the region prompts of the request -- one plan of conditioning.encode_region_prompts or one per image: K more rows
         per image, blended per latent pixel (ops.region_combine) where guidance is combined otherwise.
@@ -479,6 +539,10 @@ class PwWSampler:
         (ops.canvas_gather), evaluates the UNet on (K + 2) n_w rows and combines them into the canvas's noise prediction (ops.canvas_combine)
         for one scheduler.step on the canvas. A weight_function's score statistic (qk.max() ...) is per window, as it is per image. Raises
         ValueError while record_attention_maps() is active, and with extra_channels.
+        hold: None, or the region strengths of an img2img request: {"init": x0 and "noise": z, fp32 like `latents` (which is
+        add_noise(x0, z, timesteps[0])); "strength": S fp32 [n, h, w] in [0, 1] (ops.hold_strength_map), at canvas size for a canvas
+        request; "steps": T, "first": i0 -- `timesteps` are the steps i0 .. T - 1 of the T-step schedule}. Behind every scheduler.step, and in
+        front of on_step, one launch (ops.hold_apply; outside the captured graph) holds the pixels the next step does not release.
         extra_channels: inpaint's cat([mask, masked_image_latents]) ([n or 1, 5, h, w]) or None."""
         sch, unet, dev = self.scheduler, self.unet, latents.device
         self._errors.poll(wait=False)      # a hand-off time-out of an earlier request surfaces here (or in check_errors())
@@ -488,6 +552,7 @@ class PwWSampler:
             n, frame = self._canvas_check(canvas, latents, extra_channels)
         udt = unet.dtype if hasattr(unet, "dtype") else next(unet.parameters()).dtype
         conds, unconds = _as_list(cond, n), _as_list(uncond, n)
+        held = None if hold is None else dict(hold, table=self._hold_table(hold, latents, timesteps, extra_channels))
         blend = None
         if regions is not None:
             if any(_has_negative_maps(u) for u in unconds):
@@ -528,25 +593,29 @@ class PwWSampler:
         if extra_channels is not None and extra_channels.shape[0] != n:
             extra_channels = extra_channels.expand(n, -1, -1, -1)
         if canvas is not None:
-            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, None, on_step, None, negative_strength, blend, canvas)
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, None, on_step, None, negative_strength, blend, canvas,
+                                 hold=held)
         if rec is None:
-            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, None, negative_strength, blend)
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, None, negative_strength, blend,
+                                 hold=held)
         static = self._static_maps if self._graphed is not None else None
         rec.begin_request(n, latents.shape[-2:], static=static)      # (hipGraph mode: zeroes the static accumulators, before the first replay)
         holders = conds if folded is None else [folded]
         for d in holders:
             d[ATTN_RECORDER] = rec
         try:
-            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength, blend)
+            return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength, blend,
+                                 hold=held)
         finally:
             for d in holders:
                 d.pop(ATTN_RECORDER, None)
             rec.end_request(static=static is not None)
 
     def _denoise(self, conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength=1.0, blend=None,
-                 canvas=None):
+                 canvas=None, hold=None):
         """The loop of sample() (reference :470-506). blend: the region prompts of the request (sample()), or None. canvas: the plan of a
-        canvas request, or None -- `latents` is then the canvas, and the n images of the UNet evaluation are its windows."""
+        canvas request, or None -- `latents` is then the canvas, and the n images of the UNet evaluation are its windows. hold: the region
+        strengths of the request with their (theta, a, b) per step (_hold_table), or None."""
         sch, unet, n = self.scheduler, self.unet, latents.shape[0] if canvas is None else len(conds)
         udt = unet.dtype if hasattr(unet, "dtype") else next(unet.parameters()).dtype
         zero_function = lambda w, sigma, qk: 0.0      # noqa: E731  (the reference's unconditional pass, :493)
@@ -614,6 +683,17 @@ class PwWSampler:
             else:
                 noise_pred = eps_u + guidance_scale * (eps_c - eps_u)
             latents = sch.step(noise_pred, t, latents).prev_sample
+            if hold is not None:
+                # the pixels the next step does not release go back to the init latent at that step's noise level: one launch, in place, outside
+                # the captured graph in hipGraph mode
+                theta, a, b = hold["table"][i]
+                if latents.is_contiguous():
+                    ops.hold_apply(latents, hold["init"], hold["noise"], hold["strength"], theta, a, b)
+                else:
+                    # (an img2img latent inherits channels_last strides from the VAE's convolution and keeps them: the UNet's stock
+                    # convolutions round differently per memory layout, and a request whose strengths hold nothing is the plain call bit
+                    # for bit. The launch reads and writes NCHW memory, so such a latent goes through an NCHW copy and back.)
+                    latents.copy_(ops.hold_apply(latents.contiguous(), hold["init"], hold["noise"], hold["strength"], theta, a, b))
             if on_step is not None:
                 on_step(i, t, latents)
         # did any fused cross-attention launch of this request time out in its hand-off? One 4-byte device -> host copy behind an
