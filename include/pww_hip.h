@@ -324,8 +324,13 @@ int pww_bias_residual(const void *r, const void *v, const void *bias, void *y, i
  *   upsample  1: the input is first upsampled 2x nearest (Upsample2D), fused into the gather; stride 1 only
  *   Ho = (Hin * (1 + upsample) - 1) / stride + 1, likewise Wo.
  * y = T(residual + T(T(conv) + bias)) with the roundings of conv -> pww_bias_residual (each term only when given); fp32 accumulation.
- * Requirements: Cin, Cout multiples of 64, stride 1 or 2; PWW_ENOTSUP otherwise. tile_n / splitk: 0 = the library's choice (64 / 128 output
- * channels per tile; K split so that the launch about fills the device). With a K split the fp32 partials go to `workspace` (at least
+ * Requirements: Cin a multiple of 64, Cout a multiple of 64 or of 160, stride 1 or 2; PWW_ENOTSUP otherwise. tile_n / splitk: 0 = the library's
+ * choice (64 / 128 / 160 output channels per tile, a width that divides Cout; K split so that the launch about fills the device).
+ * THE 160-WIDE TILE IS NOT IN THIS LIBRARY: its code objects live in libpww_hip_convwide.so (pww_hip_convwide.h), which plans every
+ * descriptor exactly as this library does. Where the plan is that tile -- tile_n = 160, a Cout only 160 divides, or tile_n = 0 on a shape
+ * whose entry of the measured table is 160-wide (most SD1.5 shapes at 2 rows) -- pww_conv3x3_workspace_bytes still answers, and
+ * pww_conv3x3_fwd returns PWW_ENOTSUP with an error that names pww_convwide_fwd: ask pww_convwide_takes(desc) first and call that
+ * library when it says 1 (as pww_hip/ops.py does), or pass tile_n = 64 / 128 to stay in this one. With a K split the fp32 partials go to `workspace` (at least
  * pww_conv3x3_workspace_bytes(desc) bytes, 16-byte aligned, contents need not be initialised) and a second launch folds them in fixed
  * order: no atomics, results bitwise repeatable.
  */

@@ -34,9 +34,9 @@ const char *pww_convtail_last_error(void);
  *   x      [B][H][W][Cin]  (channels_last), zero padding 1, stride 1      w   [Cout][3][3][Cin]  (a channels_last nn.Conv2d weight)
  *   x2     [B][H][W][C2]   (channels_last), the same B, H, W              w2  [Cout][C2]         (a 1 x 1 nn.Conv2d weight, used in place)
  *   bias, bias2  [Cout], both required                                    y   [B][H][W][Cout]
- * Requirements: Cin, C2 and Cout multiples of 64, every tensor below 2^31 elements; PWW_ENOTSUP otherwise. x, w, x2, w2 and y 16-byte
- * aligned, the biases 8-byte aligned; PWW_EINVAL otherwise.
- * tile_n / splitk: 0 = the library's choice (64 / 128 output channels per tile; a measured table for the SD1.5 UNet's shapes, else a K split
+ * Requirements: Cin and C2 multiples of 64, Cout a multiple of 64 or of 160, every tensor below 2^31 elements; PWW_ENOTSUP otherwise. x, w, x2,
+ * w2 and y 16-byte aligned, the biases 8-byte aligned; PWW_EINVAL otherwise.
+ * tile_n / splitk: 0 = the library's choice (64 / 128 / 160 output channels per tile, a width that divides Cout; a measured table for the SD1.5 UNet's shapes, else a K split
  * so that the launch about fills the device). K runs over 9 Cin / 64 + C2 / 64 slabs of 64; a split boundary may fall anywhere in them.
  * With a K split the fp32 partials go to `workspace` (at least pww_convtail_workspace_bytes(desc) bytes, 16-byte aligned, contents need not
  * be initialised) and a second launch folds them in split order and applies the epilogue.

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
+#include <string.h>
 #include "../../include/pww_hip.h"
 
 // PWW_EXPERIMENTS = 1 builds libpww_hip_experiments.so: the product library plus the forms that were built, measured and NOT made a default
@@ -47,6 +49,24 @@ template <typename V8> __device__ __forceinline__ V8 zero8() {
     return __builtin_bit_cast(V8, z);
 }
 
+// The launch-sized LDS array of a kernel whose stages are above 64 KB (the 160-wide convolution tiles: 73 728 bytes), as in the attention
+// kernels; the host raises the kernel's limit (raise_lds_limit below). Only the instantiations that call it carry the declaration.
+__device__ __forceinline__ char *launch_lds() {
+    extern __shared__ __attribute__((aligned(16))) char lds_launch[];
+    return lds_launch;
+}
+
+// One 16-byte piece of a split-K partial tile (fp32 [nsplit][M][N] in the caller's workspace `ws`, at byte offset `byte_off`), stored
+// write-through. The partials are read exactly once, by the fold launch, from workgroups on every XCD -- never again through the L2 of the
+// XCD that wrote them. A plain store leaves the line dirty in that L2, and the write-back of all of them sits at the end of the launch, in
+// front of the fold; this store (buffer_store_dwordx4 ... sc1: the plain store's rate, the line leaves the XCD's L2 at once) sends the
+// bytes on their way while the workgroup's neighbours still compute. The buffer resource spans the workspace (`ws_bytes` < 4 GiB: the
+// host keeps plain stores above that), so a store outside it is dropped. Same bytes either way.
+__device__ __forceinline__ void store_partial_through(void *ws, unsigned ws_bytes, unsigned byte_off, const f32x4 &v) {
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(ws, 0, (int)ws_bytes, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, (int)byte_off, 0, 16);
+}
+
 // Swap bits 2 and 3 of a 5-bit row index. Feeding K rows to the MFMA in this order makes each
 // lane's 8 consecutive accumulator registers correspond to 8 consecutive keys (see pww_attn.hip).
 __device__ __forceinline__ int swap23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
@@ -79,9 +99,37 @@ struct DebugKnobs {
 };
 const DebugKnobs &debug_knobs();
 
+// PWW_PARTIAL_STORES=plain|through: how the split-K launches of the convolution and linear kernels store their fp32 partials
+// (store_partial_through above, or the plain 16-byte store). Read at EVERY call, so that a test flips it in-process and an A/B needs no rebuild; a launch captured into a
+// graph keeps what held at capture. Anything else, or unset: the default. A workspace of 4 GiB or more is past the buffer resource's
+// 32-bit extent and takes plain stores. Results do not depend on it. Default: plain -- measured on the SD1.5 UNet at 2 rows, write-through
+// won 3 us of the family's 1 900 per forward, less than a rebuild moves (profiles/conv_wide160.md, section 2).
+constexpr bool PARTIAL_STORES_THROUGH_DEFAULT = false;
+static inline int partial_stores_through(size_t ws_bytes) {
+    const char *e = getenv("PWW_PARTIAL_STORES");
+    const bool through = e && !strcmp(e, "plain") ? false : e && !strcmp(e, "through") ? true : PARTIAL_STORES_THROUGH_DEFAULT;
+    return through && ws_bytes < ((size_t)1 << 32) ? 1 : 0;
+}
+
 void set_error(const char *fmt, ...);
 int check_hip(hipError_t e, const char *what);
 bool arch_ok();
+
+// A kernel whose launch-sized LDS is above 64 KB (the 160-wide convolution tiles: two stages of 36 KB) needs its limit raised, once per
+// device; PWW_OK or PWW_EHIP. `done` is the caller's record for THIS kernel, one flag per device (hipFuncSetAttribute is per device): a
+// `static thread_local LdsRaised` beside the launch.
+struct LdsRaised { bool dev[8] = {false, false, false, false, false, false, false, false}; };
+template <typename K>
+static inline int raise_lds_limit(K kern, size_t lds, LdsRaised &raised) {
+    bool *done = raised.dev;
+    int dev = 0;
+    if (check_hip(hipGetDevice(&dev), "hipGetDevice")) return PWW_EHIP;
+    if (dev < 8 && done[dev]) return PWW_OK;
+    if (check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute"))
+        return PWW_EHIP;
+    if (dev < 8) done[dev] = true;
+    return PWW_OK;
+}
 
 // Kernel-only timing (pww_profile_*): if this thread armed a timing slot, hand out its event pair once.
 bool profile_take(hipEvent_t *start, hipEvent_t *stop, hipStream_t stream);

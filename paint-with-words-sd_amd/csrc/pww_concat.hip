@@ -414,6 +414,7 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __
 struct CatTailCold {
     const void *x1, *x2, *wsc, *bias, *bias2;
     int nsplit, nmain, ntail;
+    int through;            // split launches: the partials are stored write-through (pww_common.h: store_partial_through)
 };
 
 __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
@@ -438,7 +439,13 @@ __global__ void __launch_bounds__(CT_THREADS, 2) cat_tail_kernel(const T *__rest
     typedef typename Vec<T>::v8 V8;
     constexpr int BM = CT_BM, PF = CT_PF, XL = BM * 8 / CT_THREADS, WL = BN * 8 / CT_THREADS, RM = 4, RN = BN / 32;
     constexpr int XBYTES = BM * 128, STAGE = (BM + BN) * 128;
-    __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
+    // two stages: a static array, or above 64 KB (the 160-wide tile: 73 728 bytes) the launch-sized one (pww_conv.hip)
+    constexpr bool DYN = 2 * STAGE > 64 * 1024;
+    __shared__ __attribute__((aligned(16))) char lds[DYN ? 16 : 2 * STAGE];
+    auto stage = [&](int buf) -> char * {
+        if constexpr (DYN) return launch_lds() + buf * STAGE;
+        else return lds + buf * STAGE;
+    };
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
     const int ntm = (M + BM - 1) / BM;
@@ -508,7 +515,7 @@ __global__ void __launch_bounds__(CT_THREADS, 2) cat_tail_kernel(const T *__rest
         ps = cross ? C2 : ps;
     };
     auto store = [&](int p, int buf) {
-        char *base = lds + buf * STAGE;
+        char *base = stage(buf);
 #pragma unroll
         for (int i = 0; i < XL; ++i) {
             const u32x4 z = {0u, 0u, 0u, 0u};
@@ -526,7 +533,7 @@ __global__ void __launch_bounds__(CT_THREADS, 2) cat_tail_kernel(const T *__rest
 
     const int fr = lane & 15, fq = lane >> 4;
     auto compute = [&](int buf) {
-        const char *bx = lds + buf * STAGE, *bw = bx + XBYTES;
+        const char *bx = stage(buf), *bw = bx + XBYTES;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             V8 xf[RM], wf[RN];
@@ -575,6 +582,20 @@ __global__ void __launch_bounds__(CT_THREADS, 2) cat_tail_kernel(const T *__rest
         }
     }
 
+    if (split && cold.through) {                            // (uniform) the partials written through: pww_common.h, store_partial_through
+        const unsigned ws_bytes = (unsigned)cold.nsplit * (unsigned)M * (unsigned)N * 4u;      // (the host asks for this only below 4 GiB)
+#pragma unroll
+        for (int i = 0; i < RM; ++i) {
+            const int m = tm * BM + wm * 64 + i * 16 + fr;
+            if (m >= M) continue;
+#pragma unroll
+            for (int r = 0; r < RN; ++r) {
+                const int n = tn * BN + wn * (BN / 2) + r * 16 + fq * 4;
+                store_partial_through(out, ws_bytes, (((unsigned)ks * (unsigned)M + (unsigned)m) * (unsigned)N + (unsigned)n) * 4u, acc[r][i]);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < RM; ++i) {
         const int m = tm * BM + wm * 64 + i * 16 + fr;
@@ -604,7 +625,7 @@ constexpr TailTune TAIL_TUNED[] = {
     {128, 1280, 180, 40, 64, 12},
     {512, 1280, 180, 40, 128, 12}, {512, 1280, 180, 30, 128, 12}, {512, 1280, 180, 10, 128, 12},
     {2048, 640, 90, 30, 128, 6}, {2048, 640, 90, 20, 128, 6}, {2048, 640, 90, 15, 128, 6}, {2048, 640, 90, 5, 128, 6},
-    {8192, 320, 45, 15, 64, 4}, {8192, 320, 45, 10, 64, 4},
+    {8192, 320, 45, 15, 160, 4}, {8192, 320, 45, 10, 160, 4},
 };
 
 struct TailPlan {
@@ -614,10 +635,10 @@ struct TailPlan {
 // plan_tail of pww_conv_tail.hip for C2 = C1 + C2, and the two parts on the 64-channel grid
 bool cat_tail_plan(const pww_concat_tail_desc_t *d, TailPlan *p) {
     if ((d->dtype != PWW_DTYPE_F16 && d->dtype != PWW_DTYPE_BF16) || d->B < 1 || d->H < 1 || d->W < 1 || d->Cin < 64 || d->Cin % 64 != 0 || d->C1 < 64
-        || d->C1 % 64 != 0 || d->C2 < 64 || d->C2 % 64 != 0 || d->Cout < 64 || d->Cout % 64 != 0 || d->Cin > 65536 || d->C1 > 32768 || d->C2 > 32768
-        || d->Cout > 65536) {
-        set_error("concat_convtail: unsupported (dtype %d B %d %dx%d Cin %d C1 %d C2 %d Cout %d): Cin, C1, C2 and Cout multiples of 64", d->dtype, d->B,
-                  d->H, d->W, d->Cin, d->C1, d->C2, d->Cout);
+        || d->C1 % 64 != 0 || d->C2 < 64 || d->C2 % 64 != 0 || d->Cout < 64 || (d->Cout % 64 != 0 && d->Cout % 160 != 0) || d->Cin > 65536 || d->C1 > 32768
+        || d->C2 > 32768 || d->Cout > 65536) {
+        set_error("concat_convtail: unsupported (dtype %d B %d %dx%d Cin %d C1 %d C2 %d Cout %d): Cin, C1 and C2 multiples of 64, Cout of 64 or 160", d->dtype,
+                  d->B, d->H, d->W, d->Cin, d->C1, d->C2, d->Cout);
         return false;
     }
     const long M = (long)d->B * d->H * d->W, Ct = (long)d->C1 + d->C2;
@@ -632,8 +653,8 @@ bool cat_tail_plan(const pww_concat_tail_desc_t *d, TailPlan *p) {
     const TailTune *tuned = nullptr;
     for (const TailTune &t : TAIL_TUNED)
         if (t.M == p->M && t.N == d->Cout && t.nmain == p->nmain && t.ntail == p->ntail) tuned = &t;
-    p->bn = d->tile_n ? d->tile_n : tuned ? tuned->bn : (d->Cout % 128 == 0 ? 128 : 64);
-    if ((p->bn != 64 && p->bn != 128) || d->Cout % p->bn != 0) { set_error("concat_convtail: tile_n %d does not divide Cout %d", d->tile_n, d->Cout); return false; }
+    p->bn = d->tile_n ? d->tile_n : tuned ? tuned->bn : (d->Cout % 128 == 0 ? 128 : d->Cout % 64 == 0 ? 64 : 160);
+    if ((p->bn != 64 && p->bn != 128 && p->bn != 160) || d->Cout % p->bn != 0) { set_error("concat_convtail: tile_n %d does not divide Cout %d", d->tile_n, d->Cout); return false; }
     p->ntiles = (p->M + CT_BM - 1) / CT_BM * (d->Cout / p->bn);
     int ns = d->splitk;
     if (ns <= 0 && tuned && p->bn == tuned->bn) ns = tuned->nsplit;
@@ -654,7 +675,12 @@ int cat_tail_launch(const TailPlan &p, const pww_concat_tail_desc_t *d, const vo
     const int N = d->Cout;
     const dim3 grid(p.ntiles * p.nsplit), block(CT_THREADS);
     void *out = p.nsplit == 1 ? y : ws;
-    if (p.bn == 128) launch_timed(cat_tail_kernel<T, 128>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->C1, d->C2, d->H, d->W, cold);
+    if (p.bn == 160) {
+        constexpr size_t lds = 2 * (CT_BM + 160) * 128;
+        static thread_local LdsRaised raised;       // (of cat_tail_kernel<T, 160>: this function is instantiated per T)
+        if (raise_lds_limit(cat_tail_kernel<T, 160>, lds, raised)) return PWW_EHIP;
+        launch_timed(cat_tail_kernel<T, 160>, grid, block, lds, stream, xt, wt, out, p.M, N, d->Cin, d->C1, d->C2, d->H, d->W, cold);
+    } else if (p.bn == 128) launch_timed(cat_tail_kernel<T, 128>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->C1, d->C2, d->H, d->W, cold);
     else launch_timed(cat_tail_kernel<T, 64>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->C1, d->C2, d->H, d->W, cold);
     if (p.nsplit == 1) return check_hip(hipGetLastError(), "concat_convtail launch");
     const long MN = (long)p.M * N, n4 = MN / 4;
@@ -716,7 +742,7 @@ int concat_convtail_fwd(const void *x, const void *w, const void *x1, const void
         return PWW_EINVAL;
     }
     if (!arch_ok()) return PWW_ENOTSUP;
-    const CatTailCold cold{x1, x2, wsc, bias, bias2, p.nsplit, p.nmain, p.ntail};
+    const CatTailCold cold{x1, x2, wsc, bias, bias2, p.nsplit, p.nmain, p.ntail, need ? partial_stores_through(need) : 0};
     if (d->dtype == PWW_DTYPE_F16) return cat_tail_launch<f16>(p, d, x, w, cold, y, workspace, stream);
     return cat_tail_launch<bf16>(p, d, x, w, cold, y, workspace, stream);
 }

@@ -34,6 +34,9 @@ constexpr int CV_BM = 128, CV_THREADS = 256;
 // 252 VGPRs at BN 128 and the third workgroup per CU at BN 64 and measured no better than 1 (profiles/conv3x3_pipeline.md).
 constexpr int CV_PF = 2;
 
+// This file is compiled twice. As a unit of libpww_hip.so it instantiates the 64- and 128-wide tiles. The 160-wide tile's two code objects
+// do not fit under that library's size limit: pww_convwide.hip includes this file with PWW_CONV_WIDE_UNIT defined and libpww_hip_convwide.so
+// carries them (pww_convwide_*), with the same plan and table -- one source, so the two libraries cannot disagree about a shape.
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
@@ -41,6 +44,7 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __
 struct ConvCold {
     const void *bias, *residual;
     int nsplit, nslab;
+    int through;            // split launches: the partials are stored write-through (pww_common.h: store_partial_through)
 };
 
 // bijective block-id remap: consecutive logical ids (tiles that share weight columns) on one XCD (guide T1)
@@ -75,7 +79,14 @@ __global__ void __launch_bounds__(CV_THREADS, 2) conv3x3_kernel(const T *__restr
     typedef typename Vec<T>::v8 V8;
     constexpr int BM = CV_BM, PF = CV_PF, XL = BM * 8 / CV_THREADS, WL = BN * 8 / CV_THREADS, RM = 4, RN = BN / 32;
     constexpr int XBYTES = BM * 128, STAGE = (BM + BN) * 128;
-    __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
+    // two stages: a static array, or above 64 KB (the 160-wide tile: 73 728 bytes) the launch-sized one, as in the attention kernels. The
+    // narrower instantiations keep the array itself in every expression -- through a pointer their register allocation moved
+    constexpr bool DYN = 2 * STAGE > 64 * 1024;
+    __shared__ __attribute__((aligned(16))) char lds[DYN ? 16 : 2 * STAGE];
+    auto stage = [&](int buf) -> char * {
+        if constexpr (DYN) return launch_lds() + buf * STAGE;
+        else return lds + buf * STAGE;
+    };
 
     const int geo = cold.nslab >> 24;                       // (packed by the host: stride | upsample << 4)
     const int nslab = cold.nslab & 0xffffff;
@@ -128,7 +139,7 @@ __global__ void __launch_bounds__(CV_THREADS, 2) conv3x3_kernel(const T *__restr
         if (ci0 == Cin) { ci0 = 0; ++tap; }
     };
     auto store = [&](int p, int buf) {
-        char *base = lds + buf * STAGE;
+        char *base = stage(buf);
 #pragma unroll
         for (int i = 0; i < XL; ++i) {
             const u32x4 z = {0u, 0u, 0u, 0u};           // (the halo's select sits here, after the compute: the loads stay in flight across it)
@@ -146,7 +157,7 @@ __global__ void __launch_bounds__(CV_THREADS, 2) conv3x3_kernel(const T *__restr
 
     const int fr = lane & 15, fq = lane >> 4;
     auto compute = [&](int buf) {
-        const char *bx = lds + buf * STAGE, *bw = bx + XBYTES;
+        const char *bx = stage(buf), *bw = bx + XBYTES;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             V8 xf[RM], wf[RN];
@@ -201,6 +212,20 @@ __global__ void __launch_bounds__(CV_THREADS, 2) conv3x3_kernel(const T *__restr
     }
 
     // lane holds D[n = 16 r + 4 fq + j][m = 16 i + fr] of its wave's sub-tile
+    if (split && cold.through) {                            // (uniform) the partials written through: pww_common.h, store_partial_through
+        const unsigned ws_bytes = (unsigned)cold.nsplit * (unsigned)M * (unsigned)N * 4u;      // (the host asks for this only below 4 GiB)
+#pragma unroll
+        for (int i = 0; i < RM; ++i) {
+            const int m = tm * BM + wm * 64 + i * 16 + fr;
+            if (m >= M) continue;
+#pragma unroll
+            for (int r = 0; r < RN; ++r) {
+                const int n = tn * BN + wn * (BN / 2) + r * 16 + fq * 4;
+                store_partial_through(out, ws_bytes, (((unsigned)ks * (unsigned)M + (unsigned)m) * (unsigned)N + (unsigned)n) * 4u, acc[r][i]);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < RM; ++i) {
         const int m = tm * BM + wm * 64 + i * 16 + fr;
@@ -231,10 +256,11 @@ __global__ void __launch_bounds__(256) conv3x3_fold_kernel(const float *__restri
 struct ConvTune { int M, N, nslab, bn, nsplit; };
 constexpr ConvTune CONV_TUNED[] = {
     // 2 rows (batch 1 with classifier-free guidance)
-    {8192, 320, 45, 64, 3}, {8192, 320, 90, 64, 4}, {8192, 320, 135, 64, 3}, {8192, 640, 90, 128, 3},
-    {2048, 320, 45, 64, 6}, {2048, 640, 45, 64, 3}, {2048, 640, 90, 128, 6}, {2048, 640, 135, 128, 6}, {2048, 640, 180, 128, 6},
-    {2048, 640, 270, 128, 6}, {2048, 1280, 180, 128, 3},
-    {512, 640, 90, 64, 6}, {512, 1280, 90, 128, 6}, {512, 1280, 180, 128, 12}, {512, 1280, 270, 128, 12}, {512, 1280, 360, 128, 12},
+    // (the 160-wide cells: profiles/conv_wide160.md -- every shape where 160 beat the best 64 / 128 cell by more than the tool's 2 %)
+    {8192, 320, 45, 160, 2}, {8192, 320, 90, 160, 2}, {8192, 320, 135, 160, 4}, {8192, 640, 90, 160, 1},
+    {2048, 320, 45, 64, 6}, {2048, 640, 45, 64, 3}, {2048, 640, 90, 160, 4}, {2048, 640, 135, 160, 4}, {2048, 640, 180, 160, 4},
+    {2048, 640, 270, 128, 6}, {2048, 1280, 180, 160, 4},
+    {512, 640, 90, 64, 6}, {512, 1280, 90, 128, 6}, {512, 1280, 180, 160, 8}, {512, 1280, 270, 160, 8}, {512, 1280, 360, 160, 8},
     {128, 1280, 180, 64, 12}, {128, 1280, 360, 64, 24},
     // 16 rows (batch 8)
     {65536, 640, 90, 128, 1}, {16384, 1280, 180, 128, 1},
@@ -250,8 +276,9 @@ bool plan_conv(const pww_conv_desc_t *d, ConvPlan *p) {
     if (!d || d->size < sizeof(pww_conv_desc_t)) { set_error("conv3x3: descriptor missing or older than this library (size %u)", d ? d->size : 0u); return false; }
     const int up = d->upsample, s = d->stride;
     if ((d->dtype != PWW_DTYPE_F16 && d->dtype != PWW_DTYPE_BF16) || d->B < 1 || d->Hin < 1 || d->Win < 1 || d->Cin < 64 || d->Cin % 64 != 0
-        || d->Cout < 64 || d->Cout % 64 != 0 || (s != 1 && s != 2) || (up != 0 && up != 1) || (up && s != 1) || d->Cin > 65536 || d->Cout > 65536) {
-        set_error("conv3x3: unsupported (dtype %d B %d %dx%d Cin %d Cout %d stride %d upsample %d): Cin and Cout multiples of 64, stride 1 or 2, "
+        || d->Cout < 64 || (d->Cout % 64 != 0 && d->Cout % 160 != 0) || (s != 1 && s != 2) || (up != 0 && up != 1) || (up && s != 1) || d->Cin > 65536
+        || d->Cout > 65536) {
+        set_error("conv3x3: unsupported (dtype %d B %d %dx%d Cin %d Cout %d stride %d upsample %d): Cin a multiple of 64, Cout of 64 or 160, stride 1 or 2, "
                   "upsample only at stride 1", d->dtype, d->B, d->Hin, d->Win, d->Cin, d->Cout, s, up);
         return false;
     }
@@ -265,8 +292,8 @@ bool plan_conv(const pww_conv_desc_t *d, ConvPlan *p) {
     const ConvTune *tuned = nullptr;
     for (const ConvTune &t : CONV_TUNED)
         if (t.M == p->M && t.N == d->Cout && t.nslab == p->nslab) tuned = &t;
-    p->bn = d->tile_n ? d->tile_n : tuned ? tuned->bn : (d->Cout % 128 == 0 ? 128 : 64);
-    if ((p->bn != 64 && p->bn != 128) || d->Cout % p->bn != 0) { set_error("conv3x3: tile_n %d does not divide Cout %d", d->tile_n, d->Cout); return false; }
+    p->bn = d->tile_n ? d->tile_n : tuned ? tuned->bn : (d->Cout % 128 == 0 ? 128 : d->Cout % 64 == 0 ? 64 : 160);
+    if ((p->bn != 64 && p->bn != 128 && p->bn != 160) || d->Cout % p->bn != 0) { set_error("conv3x3: tile_n %d does not divide Cout %d", d->tile_n, d->Cout); return false; }
     p->ntiles = (p->M + CV_BM - 1) / CV_BM * (d->Cout / p->bn);
     int ns = d->splitk;
     if (ns <= 0 && tuned && p->bn == tuned->bn) ns = tuned->nsplit;
@@ -283,13 +310,23 @@ bool plan_conv(const pww_conv_desc_t *d, ConvPlan *p) {
 template <typename T>
 int conv_launch(const ConvPlan &p, const pww_conv_desc_t *d, const void *x, const void *w, const void *bias, const void *residual, void *y, void *ws,
                 hipStream_t stream) {
-    ConvCold cold{bias, residual, p.nsplit, p.nslab | ((d->stride | (d->upsample << 4)) << 24)};
-    const T *xt = static_cast<const T *>(x), *wt = static_cast<const T *>(w);
     const int N = d->Cout, HWo = p.Ho * p.Wo;
+    ConvCold cold{bias, residual, p.nsplit, p.nslab | ((d->stride | (d->upsample << 4)) << 24),
+                  p.nsplit > 1 ? partial_stores_through((size_t)p.nsplit * p.M * N * sizeof(float)) : 0};
+    const T *xt = static_cast<const T *>(x), *wt = static_cast<const T *>(w);
     const dim3 grid(p.ntiles * p.nsplit), block(CV_THREADS);
     void *out = p.nsplit == 1 ? y : ws;
+#ifdef PWW_CONV_WIDE_UNIT
+    if (p.bn != 160) { set_error("conv3x3: tile_n %d is launched by libpww_hip.so (pww_conv3x3_fwd)", p.bn); return PWW_ENOTSUP; }
+    constexpr size_t lds = 2 * (CV_BM + 160) * 128;
+    static thread_local LdsRaised raised;       // (of conv3x3_kernel<T, 160>: this function is instantiated per T)
+    if (raise_lds_limit(conv3x3_kernel<T, 160>, lds, raised)) return PWW_EHIP;
+    launch_timed(conv3x3_kernel<T, 160>, grid, block, lds, stream, xt, wt, out, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
+#else
+    if (p.bn == 160) { set_error("conv3x3: the 160-wide tile is launched by libpww_hip_convwide.so (pww_convwide_fwd)"); return PWW_ENOTSUP; }
     if (p.bn == 128) launch_timed(conv3x3_kernel<T, 128>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
     else launch_timed(conv3x3_kernel<T, 64>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->Hin, d->Win, p.Wo, HWo, cold);
+#endif
     if (p.nsplit == 1) return check_hip(hipGetLastError(), "conv3x3 launch");
     const long MN = (long)p.M * N, n4 = MN / 4;
     launch_timed(conv3x3_fold_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, static_cast<const float *>(ws), static_cast<T *>(y), n4,
@@ -301,6 +338,12 @@ bool al16(const void *a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
 
 }  // namespace
 
+// 1 when the plan of this descriptor (its tile_n, the table, or a Cout only 160 divides) is the 160-wide tile: the caller's choice of library
+int conv3x3_plans_wide(const pww_conv_desc_t *d) {
+    ConvPlan p;
+    return plan_conv(d, &p) && p.bn == 160 ? 1 : 0;
+}
+
 size_t conv3x3_workspace_bytes(const pww_conv_desc_t *d) {
     ConvPlan p;
     if (!plan_conv(d, &p)) return 0;
@@ -311,6 +354,12 @@ int conv3x3_fwd(const void *x, const void *w, const void *bias, const void *resi
                 size_t workspace_bytes, hipStream_t stream) {
     ConvPlan p;
     if (!plan_conv(d, &p)) return PWW_ENOTSUP;
+    // a descriptor is launched by exactly one of the two libraries this file is compiled into, decided by its plan alone
+#ifdef PWW_CONV_WIDE_UNIT
+    if (p.bn != 160) { set_error("conv3x3: tile_n %d is launched by libpww_hip.so (pww_conv3x3_fwd)", p.bn); return PWW_ENOTSUP; }
+#else
+    if (p.bn == 160) { set_error("conv3x3: the 160-wide tile is launched by libpww_hip_convwide.so (pww_convwide_fwd)"); return PWW_ENOTSUP; }
+#endif
     if (!x || !w || !y) { set_error("conv3x3: x, w and y are required"); return PWW_EINVAL; }
     if (!al16(x) || !al16(w) || !al16(y) || (reinterpret_cast<uintptr_t>(bias) & 7) || (reinterpret_cast<uintptr_t>(residual) & 7)) {
         set_error("conv3x3: x, w, y must be 16-byte aligned, bias and residual 8-byte aligned");

@@ -38,6 +38,7 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __
 struct TailCold {
     const void *x2, *w2, *bias, *bias2;
     int nsplit, nmain, ntail;
+    int through;            // split launches: the partials are stored write-through (pww_common.h: store_partial_through)
 };
 
 // bijective block-id remap: consecutive logical ids (tiles that share weight columns) on one XCD (guide T1)
@@ -65,7 +66,13 @@ __global__ void __launch_bounds__(CT_THREADS, 2) convtail_kernel(const T *__rest
     typedef typename Vec<T>::v8 V8;
     constexpr int BM = CT_BM, PF = CT_PF, XL = BM * 8 / CT_THREADS, WL = BN * 8 / CT_THREADS, RM = 4, RN = BN / 32;
     constexpr int XBYTES = BM * 128, STAGE = (BM + BN) * 128;
-    __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
+    // two stages: a static array, or above 64 KB (the 160-wide tile: 73 728 bytes) the launch-sized one (pww_conv.hip)
+    constexpr bool DYN = 2 * STAGE > 64 * 1024;
+    __shared__ __attribute__((aligned(16))) char lds[DYN ? 16 : 2 * STAGE];
+    auto stage = [&](int buf) -> char * {
+        if constexpr (DYN) return launch_lds() + buf * STAGE;
+        else return lds + buf * STAGE;
+    };
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
     const int ntm = (M + BM - 1) / BM;
@@ -129,7 +136,7 @@ __global__ void __launch_bounds__(CT_THREADS, 2) convtail_kernel(const T *__rest
         tap += wrap ? 1 : 0;
     };
     auto store = [&](int p, int buf) {
-        char *base = lds + buf * STAGE;
+        char *base = stage(buf);
 #pragma unroll
         for (int i = 0; i < XL; ++i) {
             const u32x4 z = {0u, 0u, 0u, 0u};           // (the halo's select sits here, after the compute: the loads stay in flight across it)
@@ -147,7 +154,7 @@ __global__ void __launch_bounds__(CT_THREADS, 2) convtail_kernel(const T *__rest
 
     const int fr = lane & 15, fq = lane >> 4;
     auto compute = [&](int buf) {
-        const char *bx = lds + buf * STAGE, *bw = bx + XBYTES;
+        const char *bx = stage(buf), *bw = bx + XBYTES;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             V8 xf[RM], wf[RN];
@@ -202,6 +209,20 @@ __global__ void __launch_bounds__(CT_THREADS, 2) convtail_kernel(const T *__rest
     }
 
     // lane holds D[n = 16 r + 4 fq + j][m = 16 i + fr] of its wave's sub-tile
+    if (split && cold.through) {                            // (uniform) the partials written through: pww_common.h, store_partial_through
+        const unsigned ws_bytes = (unsigned)cold.nsplit * (unsigned)M * (unsigned)N * 4u;      // (the host asks for this only below 4 GiB)
+#pragma unroll
+        for (int i = 0; i < RM; ++i) {
+            const int m = tm * BM + wm * 64 + i * 16 + fr;
+            if (m >= M) continue;
+#pragma unroll
+            for (int r = 0; r < RN; ++r) {
+                const int n = tn * BN + wn * (BN / 2) + r * 16 + fq * 4;
+                store_partial_through(out, ws_bytes, (((unsigned)ks * (unsigned)M + (unsigned)m) * (unsigned)N + (unsigned)n) * 4u, acc[r][i]);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < RM; ++i) {
         const int m = tm * BM + wm * 64 + i * 16 + fr;
@@ -234,7 +255,7 @@ constexpr TailTune TAIL_TUNED[] = {
     {128, 1280, 180, 40, 64, 12},
     {512, 1280, 180, 40, 128, 12}, {512, 1280, 180, 30, 128, 12}, {512, 1280, 180, 10, 128, 12},
     {2048, 640, 90, 30, 128, 6}, {2048, 640, 90, 20, 128, 6}, {2048, 640, 90, 15, 128, 6}, {2048, 640, 90, 5, 128, 6},
-    {8192, 320, 45, 15, 64, 4}, {8192, 320, 45, 10, 64, 4},
+    {8192, 320, 45, 15, 160, 4}, {8192, 320, 45, 10, 160, 4},        // (profiles/conv_wide160.md: 46.2 -> 39.7 and 43.8 -> 38.2 us)
 };
 
 struct TailPlan {
@@ -244,9 +265,9 @@ struct TailPlan {
 bool plan_tail(const pww_convtail_desc_t *d, TailPlan *p) {
     if (!d || d->size < sizeof(pww_convtail_desc_t)) { set_error("convtail: descriptor missing or older than this library (size %u)", d ? d->size : 0u); return false; }
     if ((d->dtype != PWW_DTYPE_F16 && d->dtype != PWW_DTYPE_BF16) || d->B < 1 || d->H < 1 || d->W < 1 || d->Cin < 64 || d->Cin % 64 != 0 || d->C2 < 64
-        || d->C2 % 64 != 0 || d->Cout < 64 || d->Cout % 64 != 0 || d->Cin > 65536 || d->C2 > 65536 || d->Cout > 65536) {
-        set_error("convtail: unsupported (dtype %d B %d %dx%d Cin %d C2 %d Cout %d): Cin, C2 and Cout multiples of 64", d->dtype, d->B, d->H, d->W, d->Cin,
-                  d->C2, d->Cout);
+        || d->C2 % 64 != 0 || d->Cout < 64 || (d->Cout % 64 != 0 && d->Cout % 160 != 0) || d->Cin > 65536 || d->C2 > 65536 || d->Cout > 65536) {
+        set_error("convtail: unsupported (dtype %d B %d %dx%d Cin %d C2 %d Cout %d): Cin and C2 multiples of 64, Cout of 64 or 160", d->dtype, d->B, d->H,
+                  d->W, d->Cin, d->C2, d->Cout);
         return false;
     }
     const long M = (long)d->B * d->H * d->W;
@@ -262,8 +283,8 @@ bool plan_tail(const pww_convtail_desc_t *d, TailPlan *p) {
     const TailTune *tuned = nullptr;
     for (const TailTune &t : TAIL_TUNED)
         if (t.M == p->M && t.N == d->Cout && t.nmain == p->nmain && t.ntail == p->ntail) tuned = &t;
-    p->bn = d->tile_n ? d->tile_n : tuned ? tuned->bn : (d->Cout % 128 == 0 ? 128 : 64);
-    if ((p->bn != 64 && p->bn != 128) || d->Cout % p->bn != 0) { set_error("convtail: tile_n %d does not divide Cout %d", d->tile_n, d->Cout); return false; }
+    p->bn = d->tile_n ? d->tile_n : tuned ? tuned->bn : (d->Cout % 128 == 0 ? 128 : d->Cout % 64 == 0 ? 64 : 160);
+    if ((p->bn != 64 && p->bn != 128 && p->bn != 160) || d->Cout % p->bn != 0) { set_error("convtail: tile_n %d does not divide Cout %d", d->tile_n, d->Cout); return false; }
     p->ntiles = (p->M + CT_BM - 1) / CT_BM * (d->Cout / p->bn);
     int ns = d->splitk;
     if (ns <= 0 && tuned && p->bn == tuned->bn) ns = tuned->nsplit;
@@ -280,12 +301,17 @@ bool plan_tail(const pww_convtail_desc_t *d, TailPlan *p) {
 template <typename T>
 int tail_launch(const TailPlan &p, const pww_convtail_desc_t *d, const void *x, const void *w, const void *x2, const void *w2, const void *bias,
                 const void *bias2, void *y, void *ws, hipStream_t stream) {
-    TailCold cold{x2, w2, bias, bias2, p.nsplit, p.nmain, p.ntail};
-    const T *xt = static_cast<const T *>(x), *wt = static_cast<const T *>(w);
     const int N = d->Cout;
+    TailCold cold{x2, w2, bias, bias2, p.nsplit, p.nmain, p.ntail, p.nsplit > 1 ? partial_stores_through((size_t)p.nsplit * p.M * N * sizeof(float)) : 0};
+    const T *xt = static_cast<const T *>(x), *wt = static_cast<const T *>(w);
     const dim3 grid(p.ntiles * p.nsplit), block(CT_THREADS);
     void *out = p.nsplit == 1 ? y : ws;
-    if (p.bn == 128) launch_timed(convtail_kernel<T, 128>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->C2, d->H, d->W, cold);
+    if (p.bn == 160) {
+        constexpr size_t lds = 2 * (CT_BM + 160) * 128;
+        static thread_local LdsRaised raised;       // (of convtail_kernel<T, 160>: this function is instantiated per T)
+        if (raise_lds_limit(convtail_kernel<T, 160>, lds, raised)) return PWW_EHIP;
+        launch_timed(convtail_kernel<T, 160>, grid, block, lds, stream, xt, wt, out, p.M, N, d->Cin, d->C2, d->H, d->W, cold);
+    } else if (p.bn == 128) launch_timed(convtail_kernel<T, 128>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->C2, d->H, d->W, cold);
     else launch_timed(convtail_kernel<T, 64>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->C2, d->H, d->W, cold);
     if (p.nsplit == 1) return check_hip(hipGetLastError(), "convtail launch");
     const long MN = (long)p.M * N, n4 = MN / 4;

@@ -45,6 +45,7 @@ struct LinCold {
     const void *bias, *residual;
     long ys, rs;            // row strides of y and the residual, in elements
     int nsplit, nslab, mode, inner;
+    int through;            // split launches: the partials are stored write-through (pww_common.h: store_partial_through)
 };
 
 // bijective block-id remap: consecutive logical ids (tiles that share weight columns) on one XCD (guide T1)
@@ -210,6 +211,21 @@ __global__ void __launch_bounds__(LN_THREADS, 2) linear_kernel(const T *__restri
     }
 
     // lane holds D[tile row = wn BN / 2 + 16 r + 4 fq + j][m = 16 i + fr] of its wave's sub-tile
+    if (split && cold.through) {                            // (uniform) the partials written through: pww_common.h, store_partial_through
+        const unsigned ws_bytes = (unsigned)cold.nsplit * (unsigned)M * (unsigned)N * 4u;      // (the host asks for this only below 4 GiB)
+#pragma unroll
+        for (int i = 0; i < RM; ++i) {
+            const int m = tm * BM + wm * 64 + i * 16 + fr;
+            if (m >= M) continue;
+#pragma unroll
+            for (int r = 0; r < RN; ++r) {
+                const int col = geglu ? (r >= RN / 2 ? cold.inner : 0) + tn * (BN / 2) + wn * (BN / 4) + (r % (RN / 2)) * 16 + fq * 4
+                                      : tn * BN + wn * (BN / 2) + r * 16 + fq * 4;
+                store_partial_through(out, ws_bytes, (((unsigned)ks * (unsigned)M + (unsigned)m) * (unsigned)N + (unsigned)col) * 4u, acc[r][i]);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < RM; ++i) {
         const int m = tm * BM + wm * 64 + i * 16 + fr;
@@ -310,7 +326,8 @@ bool plan_linear(const pww_linear_desc_t *d, LinPlan *p) {
 template <typename T>
 int linear_launch(const LinPlan &p, const pww_linear_desc_t *d, const void *x, const void *w, const void *bias, const void *residual, void *y, void *ws,
                   hipStream_t stream) {
-    LinCold cold{bias, residual, p.ys, p.rs, p.nsplit, p.nslab, d->epilogue, d->N / 2};
+    LinCold cold{bias, residual, p.ys, p.rs, p.nsplit, p.nslab, d->epilogue, d->N / 2,
+                 p.nsplit > 1 ? partial_stores_through((size_t)p.nsplit * d->M * d->N * sizeof(float)) : 0};
     const T *xt = static_cast<const T *>(x), *wt = static_cast<const T *>(w);
     const dim3 grid(p.ntiles * p.nsplit), block(LN_THREADS);
     void *out = p.nsplit == 1 ? y : ws;

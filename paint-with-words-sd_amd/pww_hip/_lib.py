@@ -35,6 +35,9 @@ CONCAT_LIB_PATH = os.environ.get("PWW_HIP_CONCAT_LIB", os.path.join(_HERE, "libp
 #   hold      region strength (img2img): the strength map of a request, its feather and the per-step hold of the pixels that are not
 #             released yet (include/pww_hip_hold.h): ops.hold_strength_map, ops.hold_apply. Its spec is in SIDE_EXTRA below.
 HOLD_LIB_PATH = os.environ.get("PWW_HIP_HOLD_LIB", os.path.join(_HERE, "libpww_hip_hold.so"))
+#   convwide  the 160-wide tile of the plain 3 x 3 convolution (csrc/pww_conv.hip compiled for that width alone: the product library is at
+#             its size limit; include/pww_hip_convwide.h): ops.conv3x3 where the plan is that tile. Its spec is in SIDE_EXTRA below.
+CONVWIDE_LIB_PATH = os.environ.get("PWW_HIP_CONVWIDE_LIB", os.path.join(_HERE, "libpww_hip_convwide.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -110,6 +113,11 @@ HOLD_EXPORTS = ("pww_hold_version", "pww_hold_last_error", "pww_hold_strength_ma
                 "pww_hold_thresholds")
 HOLD_MIN_VERSION = 100
 HOLD_MAX_COLORS, HOLD_MAX_FEATHER, HOLD_MAX_RADIUS, HOLD_MAX_STEPS = 8, 8.0, 24, 100000      # PWW_HOLD_MAX_* of the header
+
+
+# every symbol include/pww_hip_convwide.h declares for libpww_hip_convwide.so
+CONVWIDE_EXPORTS = ("pww_convwide_version", "pww_convwide_last_error", "pww_convwide_takes", "pww_convwide_workspace_bytes", "pww_convwide_fwd")
+CONVWIDE_MIN_VERSION = 100
 
 
 class AttnDesc(ctypes.Structure):
@@ -395,6 +403,12 @@ SIDE_EXTRA = {
         "pww_hold_apply": ([_vp, _vp, _vp, _vp, _f32, _f32, _f32, _i32, _i32, _i64, _vp], _int),
         "pww_hold_taps": ([_f32, _P(_f32), _i32], _int),
         "pww_hold_thresholds": ([_i32, _P(_f32)], _int)}),
+    # required: the measured table plans the 160-wide tile for most of the SD1.5 UNet's convolutions at 2 rows, and the product library has
+    # no code object for it -- there is no other implementation to fall back to
+    "convwide": dict(path="CONVWIDE_LIB_PATH", exports=CONVWIDE_EXPORTS, min_version=CONVWIDE_MIN_VERSION, missing_ok=False, needs="the 160-wide tile of conv3x3 needs it", sigs={
+        "pww_convwide_takes": ([_P(ConvDesc)], _int),
+        "pww_convwide_workspace_bytes": ([_P(ConvDesc)], _sz),
+        "pww_convwide_fwd": ([_vp, _vp, _vp, _vp, _vp, _P(ConvDesc), _vp, _sz, _vp], _int)}),
 }
 _side = {}      # name -> loaded handle
 
@@ -484,6 +498,11 @@ def load_concat():
 def load_hold():
     lib = _side.get("hold")
     return lib if lib is not None else load_side("hold")
+
+
+def load_convwide():
+    lib = _side.get("convwide")
+    return lib if lib is not None else load_side("convwide")
 
 
 class experiments:

@@ -1192,12 +1192,12 @@ def _khwc_weight(weight):
 
 def conv3x3_takes(x, weight, stride=1, upsample=False):
     """True when pww_conv3x3_fwd runs this call: a channels_last 4-d float16 / bfloat16 x on a HIP device, a [Cout, Cin, 3, 3] weight of its dtype,
-    Cin and Cout multiples of 64, stride 1 or 2 (upsample: stride 1)."""
+    Cin a multiple of 64, Cout a multiple of 64 or of 160 (the kernel's tile widths: 64, 128, 160), stride 1 or 2 (upsample: stride 1)."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in _DT and torch.is_tensor(weight) and weight.dtype == x.dtype and weight.dim() == 4):
         return False
     B, C, H, W = x.shape
     Cout = weight.shape[0]
-    return (tuple(weight.shape[1:]) == (C, 3, 3) and C % 64 == 0 and Cout % 64 == 0 and stride in (1, 2) and not (upsample and stride != 1)
+    return (tuple(weight.shape[1:]) == (C, 3, 3) and C % 64 == 0 and (Cout % 64 == 0 or Cout % 160 == 0) and Cout >= 64 and stride in (1, 2) and not (upsample and stride != 1)
             and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0
             and B * H * W * C < 2 ** 31 // 4)
 
@@ -1224,11 +1224,21 @@ def conv3x3(x, weight, bias=None, residual=None, stride=1, upsample=False, tile_
         residual = residual.contiguous(memory_format=torch.channels_last)
     d = _lib.ConvDesc(ctypes.sizeof(_lib.ConvDesc), _DT[x.dtype], B, H, W, C, Cout, int(stride), int(bool(upsample)), int(tile_n), int(splitk), 0)
     lib = _lib.load()
+    # the same entry points under another name where the plan is the 160-wide tile: its code objects live in libpww_hip_convwide.so
+    # (a required library: loading it raises when it is missing)
+    side = _lib.load_convwide()
+    wide = side.pww_convwide_takes(ctypes.byref(d)) == 1
+    ws_bytes, fwd, what = ((side.pww_convwide_workspace_bytes, side.pww_convwide_fwd, "pww_convwide_fwd") if wide else
+                           (lib.pww_conv3x3_workspace_bytes, lib.pww_conv3x3_fwd, "pww_conv3x3_fwd"))
     y = torch.empty((B, Cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    nbytes = int(lib.pww_conv3x3_workspace_bytes(ctypes.byref(d)))
+    nbytes = int(ws_bytes(ctypes.byref(d)))
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
     with torch.cuda.device(x.device):
-        _lib.check(lib.pww_conv3x3_fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(y), ctypes.byref(d), _ptr(ws), nbytes, _stream()), "pww_conv3x3_fwd")
+        rc = fwd(_ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(y), ctypes.byref(d), _ptr(ws), nbytes, _stream())
+        if wide:
+            _lib.check(rc, what, side)
+        else:
+            _lib.check(rc, what)
     return y
 
 

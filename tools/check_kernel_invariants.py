@@ -13,7 +13,11 @@ update, with correct results and slower kernels:
  3. the linear-layer GEMM kernels (csrc/pww_linear.hip): the convolution tile's register budgets, no scratch.
 
     python tools/check_kernel_invariants.py            # prints one line per check, exit code 1 on a violation
+ 4. the implicit-GEMM kernels of the 3 x 3 convolution (csrc/pww_conv.hip, pww_conv_tail.hip, pww_concat.hip) at tile widths 64, 128 and 160:
+    register budgets, no scratch, counted vmcnt waits in the steady K loop.
+
     python tools/check_kernel_invariants.py --only-linear   # the checks of csrc/pww_linear.hip alone (seconds instead of minutes)
+    python tools/check_kernel_invariants.py --only-conv     # the checks of the three convolution units alone
 """
 import os
 import re
@@ -72,6 +76,44 @@ def check_linear(check):
     check(seen == 6, "pww_linear.hip: %d code objects found (2 storage types x (2 tile widths + fold))" % seen)
 
 
+# (unit, main kernel, side-library flags): the three implicit-GEMM units of the 3 x 3 convolution
+# (pww_convwide.hip is pww_conv.hip compiled for the 160-wide tile alone: libpww_hip_convwide.so)
+CONV_UNITS = [("pww_conv.hip", "conv3x3_kernel", [], (64, 128)), ("pww_convwide.hip", "conv3x3_kernel", ["-fvisibility=hidden"], (160,)),
+              ("pww_conv_tail.hip", "convtail_kernel", ["-fvisibility=hidden"], (64, 128, 160)),
+              ("pww_concat.hip", "cat_tail_kernel", ["-fvisibility=hidden"], (64, 128, 160))]
+# tile width -> (VGPRs at most, waves per SIMD at least, MFMAs of the steady loop: 2 slabs x 2 k-steps x RN x 4)
+CONV_BUDGET = {64: (168, 3, 32), 128: (256, 2, 64), 160: (256, 2, 80)}
+
+
+def check_conv(check):
+    """csrc/pww_conv.hip, pww_conv_tail.hip, pww_concat.hip: the tile's register budgets per width (64: three workgroups per CU, 128 and 160:
+    two), no scratch, and a steady K loop whose vmcnt waits are all counted (its loads stay in flight across the barrier: no drain)."""
+    from isa_summary import kernels, mfma_loops
+    flags = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+    for unit, kern, side, widths in CONV_UNITS:
+        src = os.path.join(CSRC, unit)
+        rows = {n: r for n, r in resource_usage(src, flags + side).items() if kern in n}
+        check(sorted(int(re.search(r"Li(\d+)E", n).group(1)) for n in rows) == sorted(2 * widths),
+              "%s: %d %s code objects (2 storage types x tile widths %s)" % (unit, len(rows), kern, "/".join(str(w) for w in widths)))
+        for name, r in sorted(rows.items()):
+            bn = int(re.search(r"Li(\d+)E", name).group(1))
+            vmax, occ, _ = CONV_BUDGET[bn]
+            check(int(r["ScratchSize [bytes/lane]"]) == 0 and int(r["VGPRs"]) <= vmax and int(r["Occupancy [waves/SIMD]"]) >= occ,
+                  "%s<%s, %d>: %s VGPRs (<= %d), occupancy %s (>= %d), %s B scratch (none)" % (
+                      kern, "f16" if "DF16_" in name else "bf16", bn, r["VGPRs"], vmax, r["Occupancy [waves/SIMD]"], occ, r["ScratchSize [bytes/lane]"]))
+        with tempfile.TemporaryDirectory() as tmp:
+            asm = os.path.join(tmp, "k.s")
+            subprocess.run([HIPCC] + FLAGS + flags + side + ["-S", "--cuda-device-only", src, "-o", asm], capture_output=True, text=True, check=True)
+            for name, lines in kernels(asm):
+                if kern not in name:
+                    continue
+                bn = int(re.search(r"Li(\d+)E", name).group(1))
+                steady = [(label, waits) for label, n_mfma, waits in mfma_loops(lines) if n_mfma == CONV_BUDGET[bn][2]]
+                check(len(steady) == 1 and steady[0][1] and "vmcnt(0)" not in steady[0][1],
+                      "%s<%s, %d>: steady K loop waits %s (counted, no drain)" % (kern, "f16" if "DF16_" in name else "bf16", bn,
+                                                                                  " ".join(w[6:-1] for w in steady[0][1]) if steady else "-- loop not found"))
+
+
 def main():
     bad = []
 
@@ -80,8 +122,11 @@ def main():
         if not ok:
             bad.append(what)
 
-    if "--only-linear" in sys.argv:
-        check_linear(check)
+    if "--only-linear" in sys.argv or "--only-conv" in sys.argv:
+        if "--only-linear" in sys.argv:
+            check_linear(check)
+        if "--only-conv" in sys.argv:
+            check_conv(check)
         print("%d violation(s)" % len(bad))
         return 1 if bad else 0
 
@@ -185,6 +230,7 @@ def main():
     wf = sum(1 for i, l in enumerate(lines) if l.startswith("buffer_load") and any(x.startswith("s_cbranch_execnz") for x in lines[i + 1:i + 4]))      # (load; s_xor exec; s_cbranch_execnz = a waterfall loop)
     check(acc == 0 and wf == 0, "cross_out_kernel (bf16, d = 40): %d accumulator-file moves, %d buffer loads inside a waterfall loop (none)" % (acc, wf))
     check_linear(check)
+    check_conv(check)
     print("%d violation(s)" % len(bad))
     return 1 if bad else 0
 

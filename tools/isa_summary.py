@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Summarise kernels of a gfx950 assembly file (hipcc -S --cuda-device-only): instruction counts by class, code bytes, and the
 wait structure around the MFMAs (how many MFMAs sit directly behind an `s_waitcnt lgkmcnt(0)`: an exposed LDS latency at one
-wave per SIMD). Usage: isa_summary.py file.s [regex on the demangled name] [--dump]"""
+wave per SIMD). --loops: per loop that holds MFMAs, its vmcnt waits (counted or a drain).
+Usage: isa_summary.py file.s [regex on the demangled name] [--dump] [--loops]"""
 import re
 import subprocess
 import sys
@@ -15,7 +16,7 @@ def kernels(path):
 
 def demangle(n):
     """c++filt of this toolchain does not know DF16_ / DF16b: decode `_ZN3pww<len><name>I<template args>E...` by hand"""
-    m = re.match(r"_ZN3pww(\d+)", n)
+    m = re.match(r"_ZN3pww(?:12_GLOBAL__N_1)?(\d+)", n)      # (kernels of an unnamed namespace: the units of the GEMM tile)
     if not m:
         return n
     ln = int(m.group(1))
@@ -55,8 +56,30 @@ def main():
                     gated += 1
                 since = 1 if since is not None else None
         print("%-90s insts %6d  ~%6.1f KB  %s  mfma-behind-lgkm0 %d" % (dn[:90], len(ins), len(ins) * 6.0 / 1024, " ".join("%s=%d" % kv for kv in sorted(cnt.items())), gated))
+        if "--loops" in sys.argv:
+            for label, n_mfma, waits in mfma_loops(lines):
+                print("    loop %-12s mfma=%-4d vmcnt waits: %s" % (label, n_mfma, " ".join(waits) or "none"))
         if dump:
             print("\n".join(ins))
+
+
+def mfma_loops(lines):
+    """--loops: every innermost loop that holds MFMAs (a label and the last backward branch to it, no other loop inside) as (label, MFMAs,
+    the vmcnt waits inside in program order). A steady K loop that keeps its loads in flight waits with counts above 0: `vmcnt(0)` inside
+    it is a drain."""
+    at = {l.split(":")[0]: i for i, l in enumerate(lines) if re.match(r"\.LBB\d+_\d+:", l)}
+    loops = {}
+    for i, l in enumerate(lines):
+        m = re.match(r"\s+s_c?branch\w*\s+(?:\w+,\s*)?(\.LBB\d+_\d+)", l)
+        if m and m.group(1) in at and at[m.group(1)] < i:
+            loops[m.group(1)] = i
+    for label, end in sorted(loops.items(), key=lambda kv: at[kv[0]]):
+        if any(at[label] < at[o] and e <= end and o != label for o, e in loops.items()):
+            continue
+        body = [l.strip() for l in lines[at[label]:end]]
+        n_mfma = sum(1 for l in body if "mfma" in l.split()[0])
+        if n_mfma:
+            yield label, n_mfma, [re.search(r"vmcnt\(\d+\)", l).group(0) for l in body if l.startswith("s_waitcnt") and "vmcnt" in l]
 
 
 if __name__ == "__main__":

@@ -71,7 +71,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="2,16")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
-    ap.add_argument("--sweep", action="store_true", help="also time tile_n 64 / 128 and a range of K splits")
+    ap.add_argument("--sweep", action="store_true", help="also time tile_n 64 / 128 / 160 and a range of K splits")
     ap.add_argument("--kernels", action="store_true", help="list the stock op's kernels per shape")
     ap.add_argument("out", nargs="?")
     args = ap.parse_args()
@@ -115,15 +115,17 @@ def main():
             if args.sweep:
                 res = []
                 nslab = 9 * Cin // 64
-                for tn in (64, 128):
+                for tn in (64, 128, 160):
                     if Cout % tn:
                         continue
-                    for sk in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32):
+                    for sk in (1, 2, 3, 4, 5, 6, 8, 12, 16, 24, 32):
                         if sk > nslab // 4:
                             continue
                         res.append((replay_us(lambda: hip(tn, sk)), tn, sk))
                 res.sort()
-                best = "%.1f us @ %d, %d" % res[0] if res else ""
+                # the best cell of all, then the best cell of every tile width
+                per_width = [min(r for r in res if r[1] == tn) for tn in (64, 128, 160) if any(r[1] == tn for r in res)]
+                best = "; ".join(["%.1f us @ %d, %d" % res[0]] + ["%d: %.1f @ %d" % (tn, t, sk) for t, tn, sk in per_width]) if res else ""
             tot.setdefault(rows, [0.0, 0.0])
             tot[rows][0] += count * t_stock
             tot[rows][1] += count * t_hip

@@ -49,7 +49,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=2)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
-    ap.add_argument("--sweep", action="store_true", help="also time tile_n 64 / 128 and a range of K splits")
+    ap.add_argument("--sweep", action="store_true", help="also time tile_n 64 / 128 / 160 and a range of K splits")
     ap.add_argument("out", nargs="?")
     args = ap.parse_args()
     import pww_hip
@@ -89,7 +89,7 @@ def main():
         if args.sweep:
             res = []
             nslab = (9 * Cout + C2) // 64
-            for tn in (64, 128):
+            for tn in (64, 128, 160):
                 if Cout % tn:
                     continue
                 for sk in SPLITS:
