@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Twelve libraries come out of the same sources:
+Thirteen libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
                               measured and not made a default (include/pww_hip.h, section "experiments"). Built by the tests / tools that
@@ -25,6 +25,7 @@ Twelve libraries come out of the same sources:
                                 concat    the up blocks without torch.cat: GroupNorm and conv2 + shortcut reading the two halves of the concatenation in place
                                 hold      region strength: the strength map of an img2img request, its feather, and the per-step hold of the pixels not yet released
                                 convwide  the 160-wide tile of the plain 3 x 3 convolution: csrc/pww_conv.hip compiled for that width alone
+                                vae       the AutoencoderKL decoder: the one-head attention of head dim 512 and the tail (norm, SiLU, conv to 3 channels, image)
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -68,6 +69,7 @@ SIDE_LIBS_EXTRA = {
     "hold": ("pww_hold.hip", [], "region strength: the strength map, its feather and the per-step hold of the pixels not yet released"),
     # (pww_conv.hip: the unit IS that file, compiled for the 160-wide tile alone -- the product library has no room for its two code objects)
     "convwide": ("pww_convwide.hip", ["pww_conv.hip"], "the 160-wide tile of the plain 3 x 3 convolution"),
+    "vae": ("pww_vae.hip", [], "the AutoencoderKL decoder: one-head attention of head dim 512, and norm + SiLU + conv_out + image in two launches"),
 }
 ALL_SIDE_LIBS = {**SIDE_LIBS, **SIDE_LIBS_CONV, **SIDE_LIBS_EXTRA}
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
@@ -81,6 +83,7 @@ LIB_CANVAS, CANVAS_UNITS = SIDE_PATHS["canvas"], SIDE_UNITS["canvas"]
 LIB_CONCAT, CONCAT_UNITS = SIDE_PATHS["concat"], SIDE_UNITS["concat"]
 LIB_HOLD, HOLD_UNITS = SIDE_PATHS["hold"], SIDE_UNITS["hold"]
 LIB_CONVWIDE, CONVWIDE_UNITS = SIDE_PATHS["convwide"], SIDE_UNITS["convwide"]
+LIB_VAE, VAE_UNITS = SIDE_PATHS["vae"], SIDE_UNITS["vae"]
 SIDE_PUBLIC_HEADERS = {"canvas": ["pww_hip_regions.h"]}       # include/ headers a side library's own header includes (besides pww_hip.h)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
@@ -170,6 +173,7 @@ def build_canvas(force=False, verbose=False): return build_side("canvas", force,
 def build_concat(force=False, verbose=False): return build_side("concat", force, verbose)  # noqa: E704
 def build_hold(force=False, verbose=False): return build_side("hold", force, verbose)  # noqa: E704
 def build_convwide(force=False, verbose=False): return build_side("convwide", force, verbose)  # noqa: E704
+def build_vae(force=False, verbose=False): return build_side("vae", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):

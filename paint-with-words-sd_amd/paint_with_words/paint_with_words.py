@@ -48,8 +48,18 @@ def preprocess(image):
 
 def _pil_from_latents(vae, latents, output_type="pil"):
     """reference :48-57: decode the latents, one PIL image per batch row -- or, for the pipeline classes' other output types, the
-    [n, H, W, 3] float array of the diffusers pipeline's decode_latents (:821-833)."""
-    decoded = vae.decode((latents.clone() / 0.18215).to(vae.dtype)).sample
+    [n, H, W, 3] float array of the diffusers pipeline's decode_latents (:821-833).
+    A VAE with the AutoencoderKL decoder layout in float16 / bfloat16 on a HIP device (pww_hip.vae.covers) decodes on the native path: for
+    PIL output the 8-bit image comes off the device as it is (one uint8 copy, no float image on the host), for the float output types the
+    `.sample` form goes through the lines below. PWW_VAE=0, or any other VAE: the code below, unchanged."""
+    from pww_hip import vae as native_vae
+    if native_vae.enabled() and native_vae.covers(vae):
+        z = (latents.clone() / 0.18215).to(vae.dtype)
+        if output_type == "pil":
+            return [Image.fromarray(im) for im in native_vae.decode(vae, z, "uint8").cpu().numpy()]
+        decoded = native_vae.decode(vae, z, "sample")
+    else:
+        decoded = vae.decode((latents.clone() / 0.18215).to(vae.dtype)).sample
     pixels = (decoded / 2 + 0.5).clamp(0, 1).detach().float().cpu().permute(0, 2, 3, 1).numpy()
     if output_type != "pil":
         return pixels

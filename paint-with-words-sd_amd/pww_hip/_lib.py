@@ -38,6 +38,9 @@ HOLD_LIB_PATH = os.environ.get("PWW_HIP_HOLD_LIB", os.path.join(_HERE, "libpww_h
 #   convwide  the 160-wide tile of the plain 3 x 3 convolution (csrc/pww_conv.hip compiled for that width alone: the product library is at
 #             its size limit; include/pww_hip_convwide.h): ops.conv3x3 where the plan is that tile. Its spec is in SIDE_EXTRA below.
 CONVWIDE_LIB_PATH = os.environ.get("PWW_HIP_CONVWIDE_LIB", os.path.join(_HERE, "libpww_hip_convwide.so"))
+#   vae       the AutoencoderKL decoder: the mid block's one-head attention of head dim 512 and the tail -- conv_norm_out, SiLU, conv_out to 3
+#             channels, image -- in two launches (include/pww_hip_vae.h): pww_hip.vae. Its spec is in SIDE_EXTRA below.
+VAE_LIB_PATH = os.environ.get("PWW_HIP_VAE_LIB", os.path.join(_HERE, "libpww_hip_vae.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -120,6 +123,14 @@ CONVWIDE_EXPORTS = ("pww_convwide_version", "pww_convwide_last_error", "pww_conv
 CONVWIDE_MIN_VERSION = 100
 
 
+# every symbol include/pww_hip_vae.h declares for libpww_hip_vae.so
+VAE_EXPORTS = ("pww_vae_version", "pww_vae_last_error", "pww_vae_attn_fwd", "pww_vae_tail_workspace_bytes", "pww_vae_tail_chunks", "pww_vae_tail_stats",
+               "pww_vae_tail_fwd")
+VAE_MIN_VERSION = 100
+VAE_HEAD_DIM, VAE_TAIL_CHANNELS, VAE_TAIL_GROUPS, VAE_TAIL_MAX_CHUNKS = 512, 128, 32, 64      # PWW_VAE_* of the header
+VAE_OUT_SAMPLE, VAE_OUT_UINT8 = 0, 1
+
+
 class AttnDesc(ctypes.Structure):
     """struct pww_attn_desc (include/pww_hip.h)."""
     _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("N", ctypes.c_int32),
@@ -199,6 +210,20 @@ class ConcatTailDesc(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
                 ("Cin", ctypes.c_int32), ("C1", ctypes.c_int32), ("C2", ctypes.c_int32), ("Cout", ctypes.c_int32), ("tile_n", ctypes.c_int32),
                 ("splitk", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
+class VaeAttnDesc(ctypes.Structure):
+    """struct pww_vae_attn_desc (one-head attention of head dim 512; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("N", ctypes.c_int32), ("D", ctypes.c_int32),
+                ("scale", ctypes.c_float), ("q_batch_stride", ctypes.c_int64), ("q_row_stride", ctypes.c_int64), ("k_batch_stride", ctypes.c_int64),
+                ("k_row_stride", ctypes.c_int64), ("v_batch_stride", ctypes.c_int64), ("v_row_stride", ctypes.c_int64),
+                ("o_batch_stride", ctypes.c_int64), ("o_row_stride", ctypes.c_int64)]
+
+
+class VaeTailDesc(ctypes.Structure):
+    """struct pww_vae_tail_desc (GroupNorm + SiLU + 3 x 3 convolution to 3 channels + image; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("C", ctypes.c_int32), ("out", ctypes.c_int32), ("eps", ctypes.c_float)]
 
 
 class Region(ctypes.Structure):
@@ -409,6 +434,13 @@ SIDE_EXTRA = {
         "pww_convwide_takes": ([_P(ConvDesc)], _int),
         "pww_convwide_workspace_bytes": ([_P(ConvDesc)], _sz),
         "pww_convwide_fwd": ([_vp, _vp, _vp, _vp, _vp, _P(ConvDesc), _vp, _sz, _vp], _int)}),
+    # required where the plug runs (pww_hip/vae.py): PWW_VAE_ATTN=0 / PWW_VAE_TAIL=0 choose the stock sequences, a missing file does not
+    "vae": dict(path="VAE_LIB_PATH", exports=VAE_EXPORTS, min_version=VAE_MIN_VERSION, missing_ok=False, needs="the AutoencoderKL decoder's attention and tail need it", sigs={
+        "pww_vae_attn_fwd": ([_vp, _vp, _vp, _vp, _P(VaeAttnDesc), _vp], _int),
+        "pww_vae_tail_workspace_bytes": ([_P(VaeTailDesc)], _sz),
+        "pww_vae_tail_chunks": ([_P(VaeTailDesc)], _int),
+        "pww_vae_tail_stats": ([_vp, _vp, _P(VaeTailDesc), _vp, _sz, _vp], _int),
+        "pww_vae_tail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _P(VaeTailDesc), _vp, _sz, _vp], _int)}),
 }
 _side = {}      # name -> loaded handle
 
@@ -503,6 +535,11 @@ def load_hold():
 def load_convwide():
     lib = _side.get("convwide")
     return lib if lib is not None else load_side("convwide")
+
+
+def load_vae():
+    lib = _side.get("vae")
+    return lib if lib is not None else load_side("vae")
 
 
 class experiments:
