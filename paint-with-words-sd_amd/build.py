@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Thirteen libraries come out of the same sources:
+Fourteen libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
                               measured and not made a default (include/pww_hip.h, section "experiments"). Built by the tests / tools that
@@ -26,6 +26,8 @@ Thirteen libraries come out of the same sources:
                                 hold      region strength: the strength map of an img2img request, its feather, and the per-step hold of the pixels not yet released
                                 convwide  the 160-wide tile of the plain 3 x 3 convolution: csrc/pww_conv.hip compiled for that width alone
                                 vae       the AutoencoderKL decoder: the one-head attention of head dim 512 and the tail (norm, SiLU, conv to 3 channels, image)
+                                vaeenc    the AutoencoderKL encoder: the head (image -> conv_in), the downsamplers (csrc/pww_conv.hip compiled for stride 2
+                                          with the padding on the right and bottom only) and the tail (norm, SiLU, conv to 8 channels, quant_conv, latent)
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -70,6 +72,8 @@ SIDE_LIBS_EXTRA = {
     # (pww_conv.hip: the unit IS that file, compiled for the 160-wide tile alone -- the product library has no room for its two code objects)
     "convwide": ("pww_convwide.hip", ["pww_conv.hip"], "the 160-wide tile of the plain 3 x 3 convolution"),
     "vae": ("pww_vae.hip", [], "the AutoencoderKL decoder: one-head attention of head dim 512, and norm + SiLU + conv_out + image in two launches"),
+    # (pww_conv.hip again: included with PWW_CONV_DOWN_UNIT, the downsampler's geometry on the 64- and 128-wide tiles)
+    "vaeenc": ("pww_vaeenc.hip", ["pww_conv.hip"], "the AutoencoderKL encoder: image -> conv_in, the stride-2 downsamplers, and norm + SiLU + conv_out + quant_conv + latent in two launches"),
 }
 ALL_SIDE_LIBS = {**SIDE_LIBS, **SIDE_LIBS_CONV, **SIDE_LIBS_EXTRA}
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
@@ -84,6 +88,7 @@ LIB_CONCAT, CONCAT_UNITS = SIDE_PATHS["concat"], SIDE_UNITS["concat"]
 LIB_HOLD, HOLD_UNITS = SIDE_PATHS["hold"], SIDE_UNITS["hold"]
 LIB_CONVWIDE, CONVWIDE_UNITS = SIDE_PATHS["convwide"], SIDE_UNITS["convwide"]
 LIB_VAE, VAE_UNITS = SIDE_PATHS["vae"], SIDE_UNITS["vae"]
+LIB_VAEENC, VAEENC_UNITS = SIDE_PATHS["vaeenc"], SIDE_UNITS["vaeenc"]
 SIDE_PUBLIC_HEADERS = {"canvas": ["pww_hip_regions.h"]}       # include/ headers a side library's own header includes (besides pww_hip.h)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
@@ -174,6 +179,7 @@ def build_concat(force=False, verbose=False): return build_side("concat", force,
 def build_hold(force=False, verbose=False): return build_side("hold", force, verbose)  # noqa: E704
 def build_convwide(force=False, verbose=False): return build_side("convwide", force, verbose)  # noqa: E704
 def build_vae(force=False, verbose=False): return build_side("vae", force, verbose)  # noqa: E704
+def build_vaeenc(force=False, verbose=False): return build_side("vaeenc", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):

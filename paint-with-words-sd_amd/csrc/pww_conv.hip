@@ -37,6 +37,9 @@ constexpr int CV_PF = 2;
 // This file is compiled twice. As a unit of libpww_hip.so it instantiates the 64- and 128-wide tiles. The 160-wide tile's two code objects
 // do not fit under that library's size limit: pww_convwide.hip includes this file with PWW_CONV_WIDE_UNIT defined and libpww_hip_convwide.so
 // carries them (pww_convwide_*), with the same plan and table -- one source, so the two libraries cannot disagree about a shape.
+// A third compile, pww_vaeenc.hip with PWW_CONV_DOWN_UNIT defined, is the AutoencoderKL encoder's downsampler (libpww_hip_vaeenc.so,
+// pww_vaeenc_down_*): stride 2 with the zero padding on the right and bottom only, i.e. the pad origin at 0 and Ho = (H - 2) / 2 + 1, on
+// the 64- and 128-wide tiles. With neither macro defined the file expands to exactly what it was before that unit existed.
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
@@ -110,8 +113,13 @@ __global__ void __launch_bounds__(CV_THREADS, 2) conv3x3_kernel(const T *__restr
         m = m < M ? m : M - 1;
         const int b = m / HWo, rem = m - b * HWo, oy = rem / Wo, ox = rem - oy * Wo;
         pix[i] = b * Hin * Win;
+#ifdef PWW_CONV_DOWN_UNIT
+        y0[i] = oy * stride;        // no padding on the top and left: the taps are rows 2 oy + {0, 1, 2} (the halo test below covers the bottom and right)
+        x0[i] = ox * stride;
+#else
         y0[i] = oy * stride - 1;
         x0[i] = ox * stride - 1;
+#endif
     }
     const T *wrow = w + (long)(tn * BN + (tid >> 3)) * K9 + c * 8;
     const int swz = ((c ^ ((tid >> 3) & 7)) << 4);          // LDS byte offset of this thread's chunk within its row
@@ -283,15 +291,23 @@ bool plan_conv(const pww_conv_desc_t *d, ConvPlan *p) {
         return false;
     }
     const int Hv = d->Hin << up, Wv = d->Win << up;
+#ifdef PWW_CONV_DOWN_UNIT
+    if (s != 2 || up || Hv < 2 || Wv < 2) { set_error("conv3x3 (downsampler): stride 2, no upsample, H and W >= 2 (got stride %d, %dx%d)", s, d->Hin, d->Win); return false; }
+    p->Ho = (Hv - 2) / 2 + 1;
+    p->Wo = (Wv - 2) / 2 + 1;
+#else
     p->Ho = (Hv - 1) / s + 1;
     p->Wo = (Wv - 1) / s + 1;
+#endif
     const long M = (long)d->B * p->Ho * p->Wo;
     if ((long)d->B * d->Hin * d->Win * d->Cin >= (1L << 31) || M * d->Cout >= (1L << 31)) { set_error("conv3x3: tensor of 2^31 elements or more"); return false; }
     p->M = (int)M;
     p->nslab = 9 * d->Cin / 64;
     const ConvTune *tuned = nullptr;
+#ifndef PWW_CONV_DOWN_UNIT      // (the table was measured on the padding-1 geometry, and some of its cells are the 160-wide tile)
     for (const ConvTune &t : CONV_TUNED)
         if (t.M == p->M && t.N == d->Cout && t.nslab == p->nslab) tuned = &t;
+#endif
     p->bn = d->tile_n ? d->tile_n : tuned ? tuned->bn : (d->Cout % 128 == 0 ? 128 : d->Cout % 64 == 0 ? 64 : 160);
     if ((p->bn != 64 && p->bn != 128 && p->bn != 160) || d->Cout % p->bn != 0) { set_error("conv3x3: tile_n %d does not divide Cout %d", d->tile_n, d->Cout); return false; }
     p->ntiles = (p->M + CV_BM - 1) / CV_BM * (d->Cout / p->bn);

@@ -39,11 +39,36 @@ except Exception:  # pragma: no cover - depends on the environment
 DEFAULT_MODE = os.environ.get("PWW_MODE", "graph")
 
 
+def preprocess_uint8(image):
+    """What `preprocess` is made of: the image resized (LANCZOS) to the next lower multiple of 32, as the [1, H, W, 3] array of its pixels
+    (uint8 for an RGB image)."""
+    width, height = (side - side % 32 for side in image.size)
+    return np.array(image.resize((width, height), resample=Image.LANCZOS))[None]
+
+
 def preprocess(image):
     """reference :28-35: PIL image -> [-1, 1] NCHW tensor at the next lower multiple of 32."""
-    width, height = (side - side % 32 for side in image.size)
-    pixels = np.asarray(image.resize((width, height), resample=Image.LANCZOS), dtype=np.float32) / 255.0
-    return 2.0 * torch.from_numpy(pixels[None].transpose(0, 3, 1, 2)) - 1.0
+    pixels = preprocess_uint8(image).astype(np.float32) / 255.0
+    return 2.0 * torch.from_numpy(pixels.transpose(0, 3, 1, 2)) - 1.0
+
+
+def _encode_scaled(vae, image, device=None):
+    """0.18215 * vae.encode(image).latent_dist.sample(): the scaled latent of an init image (:461, inpaint :213-226). image: a PIL image (it is
+    preprocessed here and sent to `device`) or the tensor `vae.encode` is given.
+    A VAE with the AutoencoderKL encoder layout in float16 / bfloat16 on a HIP device (pww_hip.vae_encode.covers) encodes on the native path,
+    the noise drawn as `latent_dist.sample()` draws it; a PIL image goes there as its uint8 pixels (a quarter of the upload, no float image on
+    the host) -> the fp32 latent. PWW_VAE_ENCODE=0, or any other VAE: the stock line, unchanged -> the latent in the VAE's dtype."""
+    from pww_hip import vae_encode
+    if vae_encode.enabled() and vae_encode.covers(vae):
+        if isinstance(image, Image.Image):
+            pixels = preprocess_uint8(image)
+            if pixels.dtype == np.uint8 and pixels.ndim == 4 and pixels.shape[3] == 3:
+                return vae_encode.encode(vae, torch.from_numpy(pixels).to(device=device), noise="sample")
+            image = preprocess(image).to(device=device)
+        return vae_encode.encode(vae, image.to(vae.dtype), noise="sample")
+    if isinstance(image, Image.Image):
+        image = preprocess(image).to(device=device)
+    return 0.18215 * vae.encode(image.to(vae.dtype)).latent_dist.sample()
 
 
 def _pil_from_latents(vae, latents, output_type="pil"):
@@ -231,8 +256,7 @@ def _held_images(tools, device, seeds, timesteps, seeds_info, init_images, made_
     vae, scheduler = tools[0], tools[4]
     lats, inits, noises = [], [], []
     for init_image in init_images:
-        image = preprocess(init_image).to(device=device)
-        init_latents = 0.18215 * vae.encode(image.to(vae.dtype)).latent_dist.sample().float()
+        init_latents = _encode_scaled(vae, init_image, device).float()
         noise = torch.randn(init_latents.shape).to(device)
         lats.append(scheduler.add_noise(init_latents, noise, timesteps[:1]))
         inits.append(init_latents), noises.append(noise)

@@ -13,7 +13,8 @@ from PIL import Image
 
 from pww_hip import ops
 from .paint_with_words import (LMSDiscreteScheduler, _tools, _generate, _finish, _broadcast, _batch_requests, check_prompt_chunks,
-                               check_negative_context, check_region_prompts, check_loras, _region_requests, preprocess, _extract_seed_and_sigma_from_context)
+                               check_negative_context, check_region_prompts, check_loras, _region_requests, preprocess, _encode_scaled,
+                               _extract_seed_and_sigma_from_context)
 
 
 def _as_uint8_pixels(image, channels):
@@ -77,7 +78,7 @@ def prepare_mask_latents(vae, mask, masked_image, batch_size, height, width, dty
     """reference :109-134: mask to latent resolution (nearest), masked image through the VAE encoder, both repeated
     per batch row (and doubled for a CFG-concatenated batch)."""
     mask = F.interpolate(mask, size=(height // 8, width // 8)).to(device=device, dtype=dtype)
-    latent = 0.18215 * vae.encode(masked_image.to(device=device, dtype=vae.dtype)).latent_dist.sample()
+    latent = _encode_scaled(vae, masked_image.to(device=device, dtype=vae.dtype))
     reps = batch_size * (2 if do_classifier_free_guidance else 1)
     return mask.repeat(reps, 1, 1, 1), latent.repeat(reps, 1, 1, 1).to(device=device, dtype=dtype)
 
@@ -90,13 +91,13 @@ def _inpaint_inputs(vae, init_image, mask_image, seed, scheduler, timesteps, dev
         height, width = mask_hw
     generator = torch.manual_seed(seed)
     image = preprocess(init_image).to(device=device)
-    init_latents = 0.18215 * vae.encode(image.to(vae.dtype)).latent_dist.sample().float()
+    init_latents = _encode_scaled(vae, image).float()
     noise = torch.randn(init_latents.shape, generator=generator).to(device)
     latents = scheduler.add_noise(init_latents, noise, timesteps[:1])
 
     rgb, m8 = _as_uint8_pixels(init_image, 3), _as_uint8_pixels(mask_image, 1)
     _, masked_image, mask_lat = _prep_on_device(rgb, m8, device, lat_hw=(height // 8, width // 8))
-    masked_latents = 0.18215 * vae.encode(masked_image.to(vae.dtype)).latent_dist.sample().to(latents.dtype)
+    masked_latents = _encode_scaled(vae, masked_image).to(latents.dtype)
     if mask_hw is not None and (mask_lat.shape[-2:] != latents.shape[-2:] or masked_latents.shape[-2:] != latents.shape[-2:]):
         # the reference's pipeline fails in torch.cat here (:532): `height` / `width` must be the size of `image`
         raise ValueError(f"`height` x `width` = {height} x {width} gives a {tuple(mask_lat.shape[-2:])} latent mask but `image` gives "

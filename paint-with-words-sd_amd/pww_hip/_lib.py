@@ -41,6 +41,11 @@ CONVWIDE_LIB_PATH = os.environ.get("PWW_HIP_CONVWIDE_LIB", os.path.join(_HERE, "
 #   vae       the AutoencoderKL decoder: the mid block's one-head attention of head dim 512 and the tail -- conv_norm_out, SiLU, conv_out to 3
 #             channels, image -- in two launches (include/pww_hip_vae.h): pww_hip.vae. Its spec is in SIDE_EXTRA below.
 VAE_LIB_PATH = os.environ.get("PWW_HIP_VAE_LIB", os.path.join(_HERE, "libpww_hip_vae.so"))
+#   vaeenc    the AutoencoderKL encoder: the head (image -> conv_in, 3 input channels), the downsamplers (stride 2, padding on the right and
+#             bottom only: csrc/pww_conv.hip compiled for that geometry) and the tail -- conv_norm_out, SiLU, conv_out to 8 channels,
+#             quant_conv, mean / logvar, the scaled latent -- in two launches (include/pww_hip_vaeenc.h): pww_hip.vae_encode. Its spec is in
+#             SIDE_EXTRA below.
+VAEENC_LIB_PATH = os.environ.get("PWW_HIP_VAEENC_LIB", os.path.join(_HERE, "libpww_hip_vaeenc.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -129,6 +134,14 @@ VAE_EXPORTS = ("pww_vae_version", "pww_vae_last_error", "pww_vae_attn_fwd", "pww
 VAE_MIN_VERSION = 100
 VAE_HEAD_DIM, VAE_TAIL_CHANNELS, VAE_TAIL_GROUPS, VAE_TAIL_MAX_CHUNKS = 512, 128, 32, 64      # PWW_VAE_* of the header
 VAE_OUT_SAMPLE, VAE_OUT_UINT8 = 0, 1
+
+
+# every symbol include/pww_hip_vaeenc.h declares for libpww_hip_vaeenc.so
+VAEENC_EXPORTS = ("pww_vaeenc_version", "pww_vaeenc_last_error", "pww_vaeenc_head_fwd", "pww_vaeenc_down_workspace_bytes", "pww_vaeenc_down_fwd",
+                  "pww_vaeenc_tail_workspace_bytes", "pww_vaeenc_tail_chunks", "pww_vaeenc_tail_stats", "pww_vaeenc_tail_fwd")
+VAEENC_MIN_VERSION = 100
+VAEENC_HEAD_CHANNELS, VAEENC_TAIL_CHANNELS, VAEENC_TAIL_GROUPS, VAEENC_TAIL_MAX_CHUNKS = 128, 512, 32, 64      # PWW_VAEENC_* of the header
+VAEENC_IN_SAMPLE, VAEENC_IN_UINT8 = 0, 1
 
 
 class AttnDesc(ctypes.Structure):
@@ -224,6 +237,24 @@ class VaeTailDesc(ctypes.Structure):
     """struct pww_vae_tail_desc (GroupNorm + SiLU + 3 x 3 convolution to 3 channels + image; size-prefixed)."""
     _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
                 ("C", ctypes.c_int32), ("out", ctypes.c_int32), ("eps", ctypes.c_float)]
+
+
+class VaeEncHeadDesc(ctypes.Structure):
+    """struct pww_vaeenc_head_desc (image -> conv_in, channels_last; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("form", ctypes.c_int32)]
+
+
+class VaeEncDownDesc(ctypes.Structure):
+    """struct pww_vaeenc_down_desc (3 x 3 convolution, stride 2, padding on the right and bottom only; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32), ("tile_n", ctypes.c_int32), ("splitk", ctypes.c_int32)]
+
+
+class VaeEncTailDesc(ctypes.Structure):
+    """struct pww_vaeenc_tail_desc (GroupNorm + SiLU + conv to 8 channels + quant_conv + latent; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("C", ctypes.c_int32), ("eps", ctypes.c_float), ("scale", ctypes.c_float)]
 
 
 class Region(ctypes.Structure):
@@ -441,6 +472,15 @@ SIDE_EXTRA = {
         "pww_vae_tail_chunks": ([_P(VaeTailDesc)], _int),
         "pww_vae_tail_stats": ([_vp, _vp, _P(VaeTailDesc), _vp, _sz, _vp], _int),
         "pww_vae_tail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _P(VaeTailDesc), _vp, _sz, _vp], _int)}),
+    # required where the plug runs (pww_hip/vae_encode.py): PWW_VAE_ENC_HEAD=0 / _DOWN=0 / _TAIL=0 choose the stock sequences, a missing file does not
+    "vaeenc": dict(path="VAEENC_LIB_PATH", exports=VAEENC_EXPORTS, min_version=VAEENC_MIN_VERSION, missing_ok=False, needs="the AutoencoderKL encoder's head, downsamplers and tail need it", sigs={
+        "pww_vaeenc_head_fwd": ([_vp, _vp, _vp, _vp, _vp, _P(VaeEncHeadDesc), _vp], _int),
+        "pww_vaeenc_down_workspace_bytes": ([_P(VaeEncDownDesc)], _sz),
+        "pww_vaeenc_down_fwd": ([_vp, _vp, _vp, _vp, _P(VaeEncDownDesc), _vp, _sz, _vp], _int),
+        "pww_vaeenc_tail_workspace_bytes": ([_P(VaeEncTailDesc)], _sz),
+        "pww_vaeenc_tail_chunks": ([_P(VaeEncTailDesc)], _int),
+        "pww_vaeenc_tail_stats": ([_vp, _vp, _P(VaeEncTailDesc), _vp, _sz, _vp], _int),
+        "pww_vaeenc_tail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(VaeEncTailDesc), _vp, _sz, _vp], _int)}),
 }
 _side = {}      # name -> loaded handle
 
@@ -540,6 +580,11 @@ def load_convwide():
 def load_vae():
     lib = _side.get("vae")
     return lib if lib is not None else load_side("vae")
+
+
+def load_vaeenc():
+    lib = _side.get("vaeenc")
+    return lib if lib is not None else load_side("vaeenc")
 
 
 class experiments:

@@ -58,9 +58,27 @@ def reset_stats():
     _CALLS[0] = 0
 
 
+_ACTIVE = [_STATS]      # the counters `_count` writes to: this module's, or inside `counting(...)` those of the caller (pww_hip.vae_encode)
+
+
 def _count(part, native):
-    _STATS[part][0 if native else 1] += 1
+    _ACTIVE[0][part][0 if native else 1] += 1
     return native
+
+
+class counting:
+    """Inside `with counting(stats):` the helpers below (_group_norm, _conv, _resnet, _attention_block) count into `stats` ({part: [native,
+    stock]}) instead of this module's counters: the encoder plug runs on them and keeps counters of its own."""
+
+    def __init__(self, stats):
+        self._stats = stats
+
+    def __enter__(self):
+        self._prev, _ACTIVE[0] = _ACTIVE[0], self._stats
+
+    def __exit__(self, *exc):
+        _ACTIVE[0] = self._prev
+        return False
 
 
 # ---- the structural check ------------------------------------------------------------------------------------------------------------------

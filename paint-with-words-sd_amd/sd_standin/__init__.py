@@ -4,4 +4,4 @@ from .unet import (CrossAttention, BasicTransformerBlock, Transformer2DModel, UN
                    SD15_CONFIG, SD15_INPAINT_CONFIG, SD21_CONFIG, TINY_CONFIG, TINY_SD2_CONFIG)
 from .schedulers import LMSDiscreteScheduler, PLMSScheduler
 from .text import HashTokenizer, TinyTextEncoder, build_clip_text_encoder
-from .vae import TinyVAE, AutoencoderKL, SD_VAE_CONFIG
+from .vae import TinyVAE, AutoencoderKL, AutoencoderKLEncDec, SD_VAE_CONFIG

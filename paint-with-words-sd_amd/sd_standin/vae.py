@@ -3,7 +3,8 @@ the reference only needs ``vae.decode(z).sample`` (paint_with_words/paint_with_w
 img2img / inpaint, ``vae.encode(x).latent_dist.sample()`` (:461-462).
 
 ``TinyVAE`` is that minimum (what every loop test and bench.py use); ``AutoencoderKL`` below is the real Stable Diffusion DECODER topology
-with random seeded weights, the module `pww_hip.vae.decode` runs on the native path."""
+with random seeded weights, the module `pww_hip.vae.decode` runs on the native path; ``AutoencoderKLEncDec`` adds the real ENCODER topology
+(and `encode(x).latent_dist` as the diagonal Gaussian), the module `pww_hip.vae_encode.encode` runs on the native path."""
 from types import SimpleNamespace
 
 import torch
@@ -160,3 +161,88 @@ class AutoencoderKL(nn.Module):
     def encode(self, x):
         mean = self.enc(x.to(self.dtype))
         return SimpleNamespace(latent_dist=SimpleNamespace(sample=lambda generator=None: mean, mode=lambda: mean))
+
+
+# ---- the encoder of the same VAE, restated from the published architecture with the attribute names of diffusers 0.10.0 ---------------------
+class VaeDownsample2D(nn.Module):
+    """Stride 2 with the padding on the right and bottom only: the taps of output o are the inputs 2 o + {0, 1, 2}."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.conv = nn.Conv2d(channels, channels, 3, stride=2, padding=0)
+
+    def forward(self, x):
+        return self.conv(F.pad(x, (0, 1, 0, 1)))
+
+
+class VaeDownBlock(nn.Module):
+    def __init__(self, in_channels, out_channels, layers, add_downsample, groups, eps):
+        super().__init__()
+        self.resnets = nn.ModuleList([VaeResnetBlock2D(in_channels if i == 0 else out_channels, out_channels, groups, eps) for i in range(layers)])
+        self.downsamplers = nn.ModuleList([VaeDownsample2D(out_channels)]) if add_downsample else None
+
+    def forward(self, x):
+        for resnet in self.resnets:
+            x = resnet(x)
+        if self.downsamplers is not None:
+            x = self.downsamplers[0](x)
+        return x
+
+
+class VaeEncoder(nn.Module):
+    def __init__(self, in_channels, latent_channels, block_out_channels, layers_per_block, groups, eps):
+        super().__init__()
+        chs = list(block_out_channels)                  # SD: 128, 256, 512, 512
+        self.conv_in = nn.Conv2d(in_channels, chs[0], 3, padding=1)
+        self.down_blocks = nn.ModuleList([VaeDownBlock(chs[max(i - 1, 0)], ch, layers_per_block, i < len(chs) - 1, groups, eps) for i, ch in enumerate(chs)])
+        self.mid_block = VaeMidBlock(chs[-1], groups, eps)
+        self.conv_norm_out = nn.GroupNorm(groups, chs[-1], eps=eps)
+        self.conv_act = nn.SiLU()
+        self.conv_out = nn.Conv2d(chs[-1], 2 * latent_channels, 3, padding=1)
+
+    def forward(self, x):
+        x = self.conv_in(x)
+        for block in self.down_blocks:
+            x = block(x)
+        return self.conv_out(self.conv_act(self.conv_norm_out(self.mid_block(x))))
+
+
+class DiagonalGaussian:
+    """The posterior `encode` returns as `.latent_dist`: mean | logvar are the two halves of the moments, logvar clamped to [-30, 20]."""
+
+    def __init__(self, moments):
+        self.mean, logvar = torch.chunk(moments, 2, dim=1)
+        self.logvar = torch.clamp(logvar, -30.0, 20.0)
+        self.std = torch.exp(0.5 * self.logvar)
+
+    def sample(self, generator=None):
+        """THE statement of how the noise is drawn: fp32 normals of the mean's shape from `generator` (None: the default generator of the
+        mean's device) on the mean's device, cast to its dtype."""
+        noise = torch.randn(self.mean.shape, generator=generator, device=self.mean.device).to(self.mean.dtype)
+        return self.mean + self.std * noise
+
+    def mode(self):
+        return self.mean
+
+
+class AutoencoderKLEncDec(AutoencoderKL):
+    """AutoencoderKL with the ENCODER of the Stable Diffusion 1.x / 2.x VAE as well: encoder.conv_in (3 -> 128), four down blocks of two
+    resnets (128, 256, 512, 512 channels; the first three end in a stride-2 downsampler padded on the right and bottom only), .mid_block with
+    one AttentionBlock, .conv_norm_out / SiLU / .conv_out (512 -> 8), quant_conv (8 -> 8, 1 x 1); `encode(x).latent_dist` is the diagonal
+    Gaussian of the moments. The decoder and post_quant_conv are those of AutoencoderKL(), bit for bit: the encoder's weights come from a
+    seed of their own, drawn after the parent's. The module `pww_hip.vae_encode.encode` runs on the native path."""
+
+    def __init__(self, in_channels=3, encoder_seed=1238, **kw):
+        super().__init__(**kw)
+        cfg = dict(SD_VAE_CONFIG, **{k: v for k, v in kw.items() if k in SD_VAE_CONFIG})
+        state = torch.random.get_rng_state()
+        torch.manual_seed(encoder_seed)
+        try:
+            self.encoder = VaeEncoder(in_channels, cfg["latent_channels"], cfg["block_out_channels"], cfg["layers_per_block"], cfg["norm_num_groups"], 1e-6)
+            self.quant_conv = nn.Conv2d(2 * cfg["latent_channels"], 2 * cfg["latent_channels"], 1)
+        finally:
+            torch.random.set_rng_state(state)
+        self.requires_grad_(False)
+
+    def encode(self, x):
+        return SimpleNamespace(latent_dist=DiagonalGaussian(self.quant_conv(self.encoder(x.to(self.dtype)))))
