@@ -3,7 +3,7 @@
 No torch headers are involved: the library is plain HIP behind the C ABI of include/pww_hip.h, and
 is loaded from Python with ctypes (pww_hip/_lib.py). hipcc cross-compiles without a GPU.
 
-Fourteen libraries come out of the same sources:
+Fifteen libraries come out of the same sources:
   libpww_hip.so               the product: what the default routes and the documented switches call. `build_lib()`.
   libpww_hip_experiments.so   the same sources with -DPWW_EXPERIMENTS=1 (+ pww_cross_out.hip): the product plus the forms that were built,
                               measured and not made a default (include/pww_hip.h, section "experiments"). Built by the tests / tools that
@@ -28,6 +28,8 @@ Fourteen libraries come out of the same sources:
                                 vae       the AutoencoderKL decoder: the one-head attention of head dim 512 and the tail (norm, SiLU, conv to 3 channels, image)
                                 vaeenc    the AutoencoderKL encoder: the head (image -> conv_in), the downsamplers (csrc/pww_conv.hip compiled for stride 2
                                           with the padding on the right and bottom only) and the tail (norm, SiLU, conv to 8 channels, quant_conv, latent)
+                                text      the CLIP text encoder: the embedding gather with the first LayerNorm, the causal self-attention of at most
+                                          128 tokens with head dim 64, and QuickGELU / GELU in place
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -74,6 +76,7 @@ SIDE_LIBS_EXTRA = {
     "vae": ("pww_vae.hip", [], "the AutoencoderKL decoder: one-head attention of head dim 512, and norm + SiLU + conv_out + image in two launches"),
     # (pww_conv.hip again: included with PWW_CONV_DOWN_UNIT, the downsampler's geometry on the 64- and 128-wide tiles)
     "vaeenc": ("pww_vaeenc.hip", ["pww_conv.hip"], "the AutoencoderKL encoder: image -> conv_in, the stride-2 downsamplers, and norm + SiLU + conv_out + quant_conv + latent in two launches"),
+    "text": ("pww_text.hip", [], "the CLIP text encoder: embedding gather + LayerNorm, causal self-attention of head dim 64, QuickGELU / GELU"),
 }
 ALL_SIDE_LIBS = {**SIDE_LIBS, **SIDE_LIBS_CONV, **SIDE_LIBS_EXTRA}
 SOURCES = sorted({u[0] for u in UNITS + EXPERIMENT_UNITS})
@@ -89,6 +92,7 @@ LIB_HOLD, HOLD_UNITS = SIDE_PATHS["hold"], SIDE_UNITS["hold"]
 LIB_CONVWIDE, CONVWIDE_UNITS = SIDE_PATHS["convwide"], SIDE_UNITS["convwide"]
 LIB_VAE, VAE_UNITS = SIDE_PATHS["vae"], SIDE_UNITS["vae"]
 LIB_VAEENC, VAEENC_UNITS = SIDE_PATHS["vaeenc"], SIDE_UNITS["vaeenc"]
+LIB_TEXT, TEXT_UNITS = SIDE_PATHS["text"], SIDE_UNITS["text"]
 SIDE_PUBLIC_HEADERS = {"canvas": ["pww_hip_regions.h"]}       # include/ headers a side library's own header includes (besides pww_hip.h)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
@@ -180,6 +184,7 @@ def build_hold(force=False, verbose=False): return build_side("hold", force, ver
 def build_convwide(force=False, verbose=False): return build_side("convwide", force, verbose)  # noqa: E704
 def build_vae(force=False, verbose=False): return build_side("vae", force, verbose)  # noqa: E704
 def build_vaeenc(force=False, verbose=False): return build_side("vaeenc", force, verbose)  # noqa: E704
+def build_text(force=False, verbose=False): return build_side("text", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):

@@ -46,6 +46,9 @@ VAE_LIB_PATH = os.environ.get("PWW_HIP_VAE_LIB", os.path.join(_HERE, "libpww_hip
 #             quant_conv, mean / logvar, the scaled latent -- in two launches (include/pww_hip_vaeenc.h): pww_hip.vae_encode. Its spec is in
 #             SIDE_EXTRA below.
 VAEENC_LIB_PATH = os.environ.get("PWW_HIP_VAEENC_LIB", os.path.join(_HERE, "libpww_hip_vaeenc.so"))
+#   text      the CLIP text encoder: the embedding gather with layer 0's first LayerNorm, the causal self-attention of at most 128 tokens with
+#             head dim 64, and QuickGELU / GELU in place (include/pww_hip_text.h): pww_hip.text_encode. Its spec is in SIDE_EXTRA below.
+TEXT_LIB_PATH = os.environ.get("PWW_HIP_TEXT_LIB", os.path.join(_HERE, "libpww_hip_text.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -142,6 +145,13 @@ VAEENC_EXPORTS = ("pww_vaeenc_version", "pww_vaeenc_last_error", "pww_vaeenc_hea
 VAEENC_MIN_VERSION = 100
 VAEENC_HEAD_CHANNELS, VAEENC_TAIL_CHANNELS, VAEENC_TAIL_GROUPS, VAEENC_TAIL_MAX_CHUNKS = 128, 512, 32, 64      # PWW_VAEENC_* of the header
 VAEENC_IN_SAMPLE, VAEENC_IN_UINT8 = 0, 1
+
+
+# every symbol include/pww_hip_text.h declares for libpww_hip_text.so
+TEXT_EXPORTS = ("pww_text_version", "pww_text_last_error", "pww_text_embed_ln", "pww_text_attn_fwd", "pww_text_act")
+TEXT_MIN_VERSION = 100
+TEXT_HEAD_DIM, TEXT_MAX_TOKENS, TEXT_MAX_WIDTH = 64, 128, 4096      # PWW_TEXT_* of the header
+TEXT_ACT_QUICK_GELU, TEXT_ACT_GELU = 0, 1
 
 
 class AttnDesc(ctypes.Structure):
@@ -481,6 +491,11 @@ SIDE_EXTRA = {
         "pww_vaeenc_tail_chunks": ([_P(VaeEncTailDesc)], _int),
         "pww_vaeenc_tail_stats": ([_vp, _vp, _P(VaeEncTailDesc), _vp, _sz, _vp], _int),
         "pww_vaeenc_tail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(VaeEncTailDesc), _vp, _sz, _vp], _int)}),
+    # required where the route runs (pww_hip/text_encode.py): PWW_TEXT_EMBED=0 / _ATTN=0 / _ACT=0 choose the stock sequences, a missing file does not
+    "text": dict(path="TEXT_LIB_PATH", exports=TEXT_EXPORTS, min_version=TEXT_MIN_VERSION, missing_ok=False, needs="the CLIP text encoder's embedding, attention and activation need it", sigs={
+        "pww_text_embed_ln": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp], _int),
+        "pww_text_attn_fwd": ([_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i32, _vp], _int),
+        "pww_text_act": ([_vp, _i64, _i32, _i64, _i32, _i32, _vp], _int)}),
 }
 _side = {}      # name -> loaded handle
 
@@ -585,6 +600,11 @@ def load_vae():
 def load_vaeenc():
     lib = _side.get("vaeenc")
     return lib if lib is not None else load_side("vaeenc")
+
+
+def load_text():
+    lib = _side.get("text")
+    return lib if lib is not None else load_side("text")
 
 
 class experiments:

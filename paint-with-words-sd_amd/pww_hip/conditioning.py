@@ -291,6 +291,24 @@ def check_loras(lora, region_loras, region_prompts=None, n_requests=None, tools=
     return g, out
 
 
+def _encode_row_list(text_encoder, rows, device):
+    """The text encoder over `rows` -- [1, L] id tensors (what the tokenizer returns) or id lists of one length L -- -> R tensors [1, L, C].
+    A CLIP text model the native route covers (pww_hip.text_encode: `enabled()` and `covers()`) encodes all of them in ONE forward, and the
+    list holds its rows; any other encoder (TinyTextEncoder, fp32, CPU) is called exactly as before -- once per row, in order, with a [1, L]
+    batch each -- and the list holds the encoder's OWN outputs, so the call sites hand on the very tensors they handed on before."""
+    from . import text_encode
+    rows = [r if torch.is_tensor(r) else torch.tensor([r], dtype=torch.long) for r in rows]
+    if text_encode.enabled() and text_encode.covers(text_encoder):
+        return list(text_encode.encode(text_encoder, torch.cat(rows, dim=0)).split(1, dim=0))
+    return [text_encoder(r.to(device))[0] for r in rows]
+
+
+def encode_rows(text_encoder, rows, device):
+    """`rows` ([1, L] id tensors or id lists of one length) through the text encoder -> [R, L, C]: one native forward for a CLIP text model
+    the route covers, else one call per row exactly as before (_encode_row_list)."""
+    return torch.cat(_encode_row_list(text_encoder, rows, device), dim=0)
+
+
 def encode_region_prompts(text_encoder, tokenizer, device, color_map_rgb, region_prompts, guidance_scale, like, dtype=None,
                           region_base_weight=0.0, region_feather=0.0):
     """One request's region prompts -> its plan for the sampler:
@@ -306,13 +324,17 @@ def encode_region_prompts(text_encoder, tokenizer, device, color_map_rgb, region
     L = tokenizer.model_max_length
     k = like["CONTEXT_TENSOR"].shape[1] // L
     contexts = []
+    # the K prompts' rows (k each) through the text encoder in one call: K k tensors [1, L, C]
+    rows = []
     for _, prompt, _, _ in entries:
         if k <= 1:
-            ids = tokenizer([prompt], padding="max_length", max_length=L, truncation=True, return_tensors="pt").input_ids
-            emb = text_encoder(ids.to(device))[0]
+            rows.append(tokenizer([prompt], padding="max_length", max_length=L, truncation=True, return_tensors="pt").input_ids)
         else:
-            _, rows = chunk_prompt(tokenizer, prompt, k, k)
-            emb = torch.cat([text_encoder(torch.tensor([row], dtype=torch.long).to(device))[0] for row in rows], dim=1)
+            rows.extend(chunk_prompt(tokenizer, prompt, k, k)[1])
+    embs = _encode_row_list(text_encoder, rows, device)
+    kk = max(k, 1)
+    for j in range(len(entries)):
+        emb = embs[j] if k <= 1 else torch.cat(embs[j * kk:(j + 1) * kk], dim=1)
         if dtype is not None:
             emb = emb.to(dtype)
         ctx = {"CONTEXT_TENSOR": emb}
@@ -534,18 +556,17 @@ def _encode_text_color_inputs(text_encoder, tokenizer, device, color_map_image, 
         nz_cols = None
 
     if chunk_rows is None:
-        cond_embeddings = text_encoder(text_input.input_ids.to(device))[0]
         uncond_input = tokenizer([unconditional_input_prompt], padding="max_length",
                                  max_length=text_input.input_ids.shape[-1], return_tensors="pt")
-        uncond_embeddings = text_encoder(uncond_input.input_ids.to(device))[0]
+        cond_embeddings, uncond_embeddings = _encode_row_list(text_encoder, [text_input.input_ids, uncond_input.input_ids], device)      # one call
         uncond_lis, uncond_content = uncond_input["input_ids"][0].tolist(), None
     else:
         # every chunk through the text encoder on its own (it sees 77 positions, as it was trained), the unconditional prompt to the same k
         k = len(chunk_rows)
         uncond_content, uncond_rows = chunk_prompt(tokenizer, unconditional_input_prompt, k, k)
         uncond_lis = [t for row in uncond_rows for t in row]
-        encode = lambda rows: torch.cat([text_encoder(torch.tensor([row], dtype=torch.long).to(device))[0] for row in rows], dim=1)  # noqa: E731
-        cond_embeddings, uncond_embeddings = encode(chunk_rows), encode(uncond_rows)
+        both = _encode_row_list(text_encoder, list(chunk_rows) + list(uncond_rows), device)            # 2 k rows: one call
+        cond_embeddings, uncond_embeddings = torch.cat(both[:k], dim=1), torch.cat(both[k:], dim=1)
     if dtype is not None:
         cond_embeddings, uncond_embeddings = cond_embeddings.to(dtype), uncond_embeddings.to(dtype)
 
