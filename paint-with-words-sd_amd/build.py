@@ -63,13 +63,13 @@ SIDE_LIBS = {
 }
 # (a table of its own: SIDE_LIBS is, key for key, the loader's SIDE + SIDE_MORE, and the loader keeps this library in SIDE_CONV)
 SIDE_LIBS_CONV = {
-    "convtail": ("pww_conv_tail.hip", [], "conv2 of a ResnetBlock2D with the 1 x 1 shortcut as further K-slabs"),
+    "convtail": ("pww_conv_tail.hip", ["pww_shortcut_gemm.h"], "conv2 of a ResnetBlock2D with the 1 x 1 shortcut as further K-slabs"),
 }
 # (the open-ended table: SIDE_LIBS and SIDE_LIBS_CONV are closed -- the loader's SIDE + SIDE_MORE and SIDE_CONV, key for key -- and every later
 # side library is a row here and in the loader's SIDE_EXTRA, whatever it is for)
 SIDE_LIBS_EXTRA = {
     "canvas": ("pww_canvas.hip", [], "canvases larger than the UNet's window: the windows' gather and the combine of their noise predictions"),
-    "concat": ("pww_concat.hip", [], "the up blocks without torch.cat: GroupNorm and conv2 + shortcut over the two halves of the concatenation"),
+    "concat": ("pww_concat.hip", ["pww_shortcut_gemm.h"], "the up blocks without torch.cat: GroupNorm and conv2 + shortcut over the two halves of the concatenation"),
     "hold": ("pww_hold.hip", [], "region strength: the strength map, its feather and the per-step hold of the pixels not yet released"),
     # (pww_conv.hip: the unit IS that file, compiled for the 160-wide tile alone -- the product library has no room for its two code objects)
     "convwide": ("pww_convwide.hip", ["pww_conv.hip"], "the 160-wide tile of the plain 3 x 3 convolution"),

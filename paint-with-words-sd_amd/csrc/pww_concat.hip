@@ -9,14 +9,18 @@
 //                               one source when C1 and C2 are multiples of 8: it selects base pointer, row pitch and channel offset ONCE,
 //                               in front of its first load. Nothing else moves: no load under a condition, the same loads in flight, the
 //                               same summation order, fp32 / fp64 split and f16 pivot. A group may straddle the boundary.
-//   pww_concat_convtail_fwd     convtail_kernel of pww_conv_tail.hip with the tail's input in two parts: tail slab t reads x1 (pitch C1)
-//                               when 64 t < C1, else x2 (pitch C2, channel 64 t - C1), by wave-uniform selects like the body / tail choice.
+//   pww_concat_convtail_fwd     the kernel of pww_convtail_fwd (pww_shortcut_gemm.h) with the tail's input in two parts: tail slab t reads
+//                               x1 (pitch C1) when 64 t < C1, else x2 (pitch C2, channel 64 t - C1), by wave-uniform selects like the body /
+//                               tail choice.
 //
 // Launch form, slab and apply sizes (cat_gn_plan) and tile, K order, split boundaries, fold and TAIL_TUNED (cat_tail_plan) are those of the
 // one-source entry points for C = C1 + C2: the results are BITWISE those of pww_group_norm_fwd / pww_convtail_fwd on the concatenated
-// tensor (tests/test_concat_gpu.py holds every form, tile width and split to torch.equal). The kernels are WRITTEN AGAIN here, as in
-// pww_linear.hip and pww_conv_tail.hip: a header shared with pww_norm.hip / pww_conv_tail.hip would move the register allocation and the
-// wait counts of their code objects, and those are what their measured times rest on. A change to either plan there is a change here.
+// tensor (tests/test_concat_gpu.py holds every form, tile width and split to torch.equal). The GroupNorm kernels are written again here,
+// as in pww_linear.hip: they differ from those of pww_norm.hip in kernarg layout, in the `pre` / `add` code and in the written-out
+// v_fma_mixlo_f16, and a header shared with that unit would move its code objects; a change to its plan is a change to cat_gn_plan. The
+// conv2 + shortcut kernel is NOT a copy: it is the one `__global__` template of pww_shortcut_gemm.h, instantiated here with two parts and
+// this unit's cold struct, and in pww_conv_tail.hip with one. Sharing it that way leaves all sixteen code objects of the two units as
+// they were; a `__device__` body behind two `__global__` wrappers did not (profiles/shortcut_gemm.md). Plan, fold and launch come with it.
 //
 // Kernarg preload (14 dwords): the GroupNorm kernels carry x1, x2, the partials' pointer (the apply kernel's first loads), C1, C2, HW, G,
 // cg, nslab, slab_px and apply_px hot -- what a wave needs to issue its first loads; gamma, beta, y and eps travel in the cold struct
@@ -26,6 +30,7 @@
 #define PWW_SIDE_LIB "libpww_hip_concat"
 #include "pww_side_host.h"
 #include "../../include/pww_hip_concat.h"
+#include "pww_shortcut_gemm.h"
 
 #define PWW_CONCAT_API extern "C" __attribute__((visibility("default")))
 
@@ -403,13 +408,7 @@ int cat_gn_launch(const CatGnParams &p, const pww_concat_gn_desc_t *d, const Cat
     return check_hip(hipGetLastError(), "concat_group_norm launch");
 }
 
-// ==== conv2 + shortcut over two sources (pww_conv_tail.hip) ============================================================================
-constexpr int CT_BM = 128, CT_THREADS = 256;
-constexpr int CT_PF = 2;        // K-slabs of global loads in flight while one is computed
-
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
+// ==== conv2 + shortcut over two sources (pww_shortcut_gemm.h) ===========================================================================
 // cold kernel arguments. nmain = 9 Cin / 64 slabs of the 3 x 3 gather, ntail = (C1 + C2) / 64 of the shortcut, the first C1 / 64 of them in x1
 struct CatTailCold {
     const void *x1, *x2, *wsc, *bias, *bias2;
@@ -417,222 +416,7 @@ struct CatTailCold {
     int through;            // split launches: the partials are stored write-through (pww_common.h: store_partial_through)
 };
 
-__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
-    const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-}
-
-template <typename T>
-__device__ __forceinline__ void epilogue4(const f32x4 &a, const CatTailCold &cold, T *y, long off, int n) {
-    typedef typename Vec<T>::v4 V4;
-    const V4 b = *reinterpret_cast<const V4 *>(reinterpret_cast<const T *>(cold.bias) + n);
-    const V4 b2 = *reinterpret_cast<const V4 *>(reinterpret_cast<const T *>(cold.bias2) + n);
-    V4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = (T)(a[j] + (float)b[j] + (float)b2[j]);
-    *reinterpret_cast<V4 *>(y + off) = o;
-}
-
-template <typename T, int BN>
-__global__ void __launch_bounds__(CT_THREADS, 2) cat_tail_kernel(const T *__restrict__ x, const T *__restrict__ w, void *__restrict__ out, int M, int N,
-                                                                 int Cin, int C1, int C2, int H, int W, const CatTailCold cold) {
-    typedef typename Vec<T>::v8 V8;
-    constexpr int BM = CT_BM, PF = CT_PF, XL = BM * 8 / CT_THREADS, WL = BN * 8 / CT_THREADS, RM = 4, RN = BN / 32;
-    constexpr int XBYTES = BM * 128, STAGE = (BM + BN) * 128;
-    // two stages: a static array, or above 64 KB (the 160-wide tile: 73 728 bytes) the launch-sized one (pww_conv.hip)
-    constexpr bool DYN = 2 * STAGE > 64 * 1024;
-    __shared__ __attribute__((aligned(16))) char lds[DYN ? 16 : 2 * STAGE];
-    auto stage = [&](int buf) -> char * {
-        if constexpr (DYN) return launch_lds() + buf * STAGE;
-        else return lds + buf * STAGE;
-    };
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-    const int ntm = (M + BM - 1) / BM;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const bool split = cold.nsplit > 1;
-    const int tile = bid / cold.nsplit, ks = bid - tile * cold.nsplit;
-    const int tm = tile % ntm, tn = tile / ntm;
-    const int nmain = cold.nmain, nslab = nmain + cold.ntail;
-    const int s_begin = (int)((long)ks * nslab / cold.nsplit), s_end = (int)((long)(ks + 1) * nslab / cold.nsplit);
-    const int K9 = 9 * Cin, HW = H * W, Ct = C1 + C2;
-    const T *__restrict__ xa = reinterpret_cast<const T *>(cold.x1);
-    const T *__restrict__ xb2 = reinterpret_cast<const T *>(cold.x2);
-    const T *__restrict__ w2 = reinterpret_cast<const T *>(cold.wsc);
-
-    const int c = tid & 7;
-    int pix[XL], y0[XL], x0[XL];
-#pragma unroll
-    for (int i = 0; i < XL; ++i) {
-        int m = tm * BM + (tid >> 3) + 32 * i;
-        m = m < M ? m : M - 1;
-        const int b = m / HW, rem = m - b * HW, oy = rem / W, ox = rem - oy * W;
-        pix[i] = b * HW;
-        y0[i] = oy - 1;
-        x0[i] = ox - 1;
-    }
-    const unsigned wrow = (unsigned)(tn * BN + (tid >> 3));
-    const unsigned woff_main = wrow * (unsigned)K9 + c * 8, woff_tail = wrow * (unsigned)Ct + c * 8;
-    const int swz = ((c ^ ((tid >> 3) & 7)) << 4);
-
-    u32x4 xr[PF][XL], wr[PF][WL];
-    unsigned xok[PF];
-    // K position of the next slab: tap 0 .. 8 of the gather, channel ci0 of it; tap 9 = the shortcut, ci0 its channel in the concatenation
-    const bool tail0 = s_begin >= nmain;
-    int tap = tail0 ? 9 : s_begin / (Cin >> 6);
-    int ci0 = tail0 ? (s_begin - nmain) << 6 : (s_begin - tap * (Cin >> 6)) << 6;
-    int kmain = s_begin * 64;
-    // the tail slab's source: x1 while ci0 < C1, then x2 with its channel origin folded into the pointer (x2 - C1: only ever dereferenced
-    // at ci0 >= C1), so that a tail address is `base + pixel * pitch + ci0` for both; switched by a select when ci0 reaches C1
-    const bool second0 = tail0 && ci0 >= C1;
-    const T *xs = second0 ? xb2 - C1 : xa;
-    int ps = second0 ? C2 : C1;
-    auto load = [&](int p) {
-        const bool tail = tap >= 9;                         // (uniform: selects of base, pitch and tap; every load below is issued)
-        const int ky = tail ? 1 : tap / 3, kx = tail ? 1 : tap - (tap / 3) * 3;
-        const T *xb = tail ? xs : x;
-        const T *wb = tail ? w2 : w;
-        const int pitch = tail ? ps : Cin;
-        const unsigned wpitch = (unsigned)(tail ? Ct : K9);
-        const unsigned wo = (tail ? woff_tail : woff_main) + (unsigned)(tail ? ci0 : kmain);
-        xok[p] = 0;
-#pragma unroll
-        for (int i = 0; i < XL; ++i) {
-            const int iy = y0[i] + ky, ix = x0[i] + kx;
-            const bool ok = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;     // (the centre tap is always inside)
-            xr[p][i] = *reinterpret_cast<const u32x4 *>(xb + (unsigned)((pix[i] + (ok ? iy : 0) * W + (ok ? ix : 0)) * pitch + ci0 + c * 8));
-            xok[p] |= (unsigned)ok << i;
-        }
-#pragma unroll
-        for (int j = 0; j < WL; ++j) wr[p][j] = *reinterpret_cast<const u32x4 *>(wb + (wo + (unsigned)(32 * j) * wpitch));
-        kmain += 64;
-        ci0 += 64;
-        const bool wrap = ci0 == Cin && !tail;              // (the last tap wraps into the tail: tap 9, channel 0)
-        ci0 = wrap ? 0 : ci0;
-        tap += wrap ? 1 : 0;
-        const bool cross = ci0 == C1 && tail;               // (uniform: the next tail slab is the first of x2)
-        xs = cross ? xb2 - C1 : xs;
-        ps = cross ? C2 : ps;
-    };
-    auto store = [&](int p, int buf) {
-        char *base = stage(buf);
-#pragma unroll
-        for (int i = 0; i < XL; ++i) {
-            const u32x4 z = {0u, 0u, 0u, 0u};
-            *reinterpret_cast<u32x4 *>(base + ((tid >> 3) + 32 * i) * 128 + swz) = (xok[p] >> i) & 1u ? xr[p][i] : z;
-        }
-#pragma unroll
-        for (int j = 0; j < WL; ++j) *reinterpret_cast<u32x4 *>(base + XBYTES + ((tid >> 3) + 32 * j) * 128 + swz) = wr[p][j];
-    };
-
-    f32x4 acc[RN][RM];
-#pragma unroll
-    for (int r = 0; r < RN; ++r)
-#pragma unroll
-        for (int i = 0; i < RM; ++i) acc[r][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int fr = lane & 15, fq = lane >> 4;
-    auto compute = [&](int buf) {
-        const char *bx = stage(buf), *bw = bx + XBYTES;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            V8 xf[RM], wf[RN];
-#pragma unroll
-            for (int q = 0; q < RM; ++q) {
-                const int row = wm * 64 + q * 16 + fr;
-                xf[q] = *reinterpret_cast<const V8 *>(bx + row * 128 + (((kk * 4 + fq) ^ (row & 7)) << 4));
-            }
-#pragma unroll
-            for (int r = 0; r < RN; ++r) {
-                const int row = wn * (BN / 2) + r * 16 + fr;
-                wf[r] = *reinterpret_cast<const V8 *>(bw + row * 128 + (((kk * 4 + fq) ^ (row & 7)) << 4));
-            }
-#pragma unroll
-            for (int r = 0; r < RN; ++r)
-#pragma unroll
-                for (int q = 0; q < RM; ++q) acc[r][q] = mfma16(wf[r], xf[q], acc[r][q]);
-        }
-    };
-
-    const int n = s_end - s_begin;
-    load(0);
-#pragma unroll
-    for (int p = 1; p < PF; ++p)
-        if (p < n) load(p);
-    store(0, 0);
-    __syncthreads();
-    int i = 0;
-    for (; i + 2 * PF <= n; i += PF) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            load(p);
-            compute((i + p) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-            store((p + 1) % PF, (i + p + 1) & 1);
-            __syncthreads();
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 2 * PF - 1; ++t) {
-        if (i + t < n) {
-            if (i + t + PF < n) load(t % PF);
-            compute((i + t) & 1);
-            if (i + t + 1 < n) store((t + 1) % PF, (i + t + 1) & 1);
-            __syncthreads();
-        }
-    }
-
-    if (split && cold.through) {                            // (uniform) the partials written through: pww_common.h, store_partial_through
-        const unsigned ws_bytes = (unsigned)cold.nsplit * (unsigned)M * (unsigned)N * 4u;      // (the host asks for this only below 4 GiB)
-#pragma unroll
-        for (int i = 0; i < RM; ++i) {
-            const int m = tm * BM + wm * 64 + i * 16 + fr;
-            if (m >= M) continue;
-#pragma unroll
-            for (int r = 0; r < RN; ++r) {
-                const int n = tn * BN + wn * (BN / 2) + r * 16 + fq * 4;
-                store_partial_through(out, ws_bytes, (((unsigned)ks * (unsigned)M + (unsigned)m) * (unsigned)N + (unsigned)n) * 4u, acc[r][i]);
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < RM; ++i) {
-        const int m = tm * BM + wm * 64 + i * 16 + fr;
-        if (m >= M) continue;
-#pragma unroll
-        for (int r = 0; r < RN; ++r) {
-            const int n = tn * BN + wn * (BN / 2) + r * 16 + fq * 4;
-            if (split) *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(out) + ((long)ks * M + m) * N + n) = acc[r][i];
-            else epilogue4<T>(acc[r][i], cold, reinterpret_cast<T *>(out), (long)m * N + n, n);
-        }
-    }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256) cat_tail_fold_kernel(const float *__restrict__ ws, T *__restrict__ y, long n4, int N, long MN, const CatTailCold cold) {
-    const long q = (long)blockIdx.x * 256 + threadIdx.x;
-    if (q >= n4) return;
-    const long off = q * 4;
-    f32x4 a = *reinterpret_cast<const f32x4 *>(ws + off);
-    for (int s = 1; s < cold.nsplit; ++s) a += *reinterpret_cast<const f32x4 *>(ws + s * MN + off);
-    epilogue4<T>(a, cold, y, off, (int)(off % N));
-}
-
-// TAIL_TUNED of pww_conv_tail.hip (M, N, slabs of the gather, slabs of the shortcut = (C1 + C2) / 64, tile width, split)
-struct TailTune { int M, N, nmain, ntail, bn, nsplit; };
-constexpr TailTune TAIL_TUNED[] = {
-    {128, 1280, 180, 40, 64, 12},
-    {512, 1280, 180, 40, 128, 12}, {512, 1280, 180, 30, 128, 12}, {512, 1280, 180, 10, 128, 12},
-    {2048, 640, 90, 30, 128, 6}, {2048, 640, 90, 20, 128, 6}, {2048, 640, 90, 15, 128, 6}, {2048, 640, 90, 5, 128, 6},
-    {8192, 320, 45, 15, 160, 4}, {8192, 320, 45, 10, 160, 4},
-};
-
-struct TailPlan {
-    int M, bn, nsplit, nmain, ntail, ntiles;
-};
-
-// plan_tail of pww_conv_tail.hip for C2 = C1 + C2, and the two parts on the 64-channel grid
+// the checks of pww_convtail_fwd for C2 = C1 + C2 with the two parts on the 64-channel grid, then the shared plan
 bool cat_tail_plan(const pww_concat_tail_desc_t *d, TailPlan *p) {
     if ((d->dtype != PWW_DTYPE_F16 && d->dtype != PWW_DTYPE_BF16) || d->B < 1 || d->H < 1 || d->W < 1 || d->Cin < 64 || d->Cin % 64 != 0 || d->C1 < 64
         || d->C1 % 64 != 0 || d->C2 < 64 || d->C2 % 64 != 0 || d->Cout < 64 || (d->Cout % 64 != 0 && d->Cout % 160 != 0) || d->Cin > 65536 || d->C1 > 32768
@@ -646,47 +430,7 @@ bool cat_tail_plan(const pww_concat_tail_desc_t *d, TailPlan *p) {
         set_error("concat_convtail: tensor of 2^31 elements or more");
         return false;
     }
-    p->M = (int)M;
-    p->nmain = 9 * d->Cin / 64;
-    p->ntail = (int)(Ct / 64);
-    const int nslab = p->nmain + p->ntail;
-    const TailTune *tuned = nullptr;
-    for (const TailTune &t : TAIL_TUNED)
-        if (t.M == p->M && t.N == d->Cout && t.nmain == p->nmain && t.ntail == p->ntail) tuned = &t;
-    p->bn = d->tile_n ? d->tile_n : tuned ? tuned->bn : (d->Cout % 128 == 0 ? 128 : d->Cout % 64 == 0 ? 64 : 160);
-    if ((p->bn != 64 && p->bn != 128 && p->bn != 160) || d->Cout % p->bn != 0) { set_error("concat_convtail: tile_n %d does not divide Cout %d", d->tile_n, d->Cout); return false; }
-    p->ntiles = (p->M + CT_BM - 1) / CT_BM * (d->Cout / p->bn);
-    int ns = d->splitk;
-    if (ns <= 0 && tuned && p->bn == tuned->bn) ns = tuned->nsplit;
-    if (ns <= 0) {
-        ns = (480 + p->ntiles / 2) / p->ntiles;
-        if (ns > nslab / 8) ns = nslab / 8;
-        if (ns < 1) ns = 1;
-    }
-    if (ns > nslab || ns > 64) { set_error("concat_convtail: split %d exceeds the %d K-slabs (or 64)", ns, nslab); return false; }
-    p->nsplit = ns;
-    return true;
-}
-
-template <typename T>
-int cat_tail_launch(const TailPlan &p, const pww_concat_tail_desc_t *d, const void *x, const void *w, const CatTailCold &cold, void *y, void *ws,
-                    hipStream_t stream) {
-    const T *xt = static_cast<const T *>(x), *wt = static_cast<const T *>(w);
-    const int N = d->Cout;
-    const dim3 grid(p.ntiles * p.nsplit), block(CT_THREADS);
-    void *out = p.nsplit == 1 ? y : ws;
-    if (p.bn == 160) {
-        constexpr size_t lds = 2 * (CT_BM + 160) * 128;
-        static thread_local LdsRaised raised;       // (of cat_tail_kernel<T, 160>: this function is instantiated per T)
-        if (raise_lds_limit(cat_tail_kernel<T, 160>, lds, raised)) return PWW_EHIP;
-        launch_timed(cat_tail_kernel<T, 160>, grid, block, lds, stream, xt, wt, out, p.M, N, d->Cin, d->C1, d->C2, d->H, d->W, cold);
-    } else if (p.bn == 128) launch_timed(cat_tail_kernel<T, 128>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->C1, d->C2, d->H, d->W, cold);
-    else launch_timed(cat_tail_kernel<T, 64>, grid, block, 0, stream, xt, wt, out, p.M, N, d->Cin, d->C1, d->C2, d->H, d->W, cold);
-    if (p.nsplit == 1) return check_hip(hipGetLastError(), "concat_convtail launch");
-    const long MN = (long)p.M * N, n4 = MN / 4;
-    launch_timed(cat_tail_fold_kernel<T>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, static_cast<const float *>(ws), static_cast<T *>(y), n4,
-                 N, MN, cold);
-    return check_hip(hipGetLastError(), "concat_convtail fold launch");
+    return plan_tail("concat_convtail", (int)M, 9 * d->Cin / 64, (int)(Ct / 64), d->Cout, d->tile_n, d->splitk, p);
 }
 
 }  // namespace
@@ -722,7 +466,7 @@ int concat_group_norm_fwd(const void *x1, const void *x2, const void *gamma, con
 size_t concat_convtail_workspace_bytes(const pww_concat_tail_desc_t *d) {
     TailPlan p;
     if (!desc_ok(d, d ? d->size : 0u, sizeof(pww_concat_tail_desc_t), "concat_convtail") || !cat_tail_plan(d, &p)) return 0;
-    return p.nsplit > 1 ? (size_t)p.nsplit * p.M * d->Cout * sizeof(float) : 0;
+    return tail_workspace_bytes(p, d->Cout);
 }
 
 int concat_convtail_fwd(const void *x, const void *w, const void *x1, const void *x2, const void *wsc, const void *bias, const void *bias2, void *y,
@@ -736,15 +480,15 @@ int concat_convtail_fwd(const void *x, const void *w, const void *x1, const void
         set_error("concat_convtail: x, w, x1, x2, wsc, y must be 16-byte aligned, the biases 8-byte aligned");
         return PWW_EINVAL;
     }
-    const size_t need = p.nsplit > 1 ? (size_t)p.nsplit * p.M * d->Cout * sizeof(float) : 0;
+    const size_t need = tail_workspace_bytes(p, d->Cout);
     if (need && (!workspace || !aligned16(workspace) || workspace_bytes < need)) {
         set_error("concat_convtail: split %d needs a 16-byte aligned workspace of %zu bytes (got %zu)", p.nsplit, need, workspace_bytes);
         return PWW_EINVAL;
     }
     if (!arch_ok()) return PWW_ENOTSUP;
-    const CatTailCold cold{x1, x2, wsc, bias, bias2, p.nsplit, p.nmain, p.ntail, need ? partial_stores_through(need) : 0};
-    if (d->dtype == PWW_DTYPE_F16) return cat_tail_launch<f16>(p, d, x, w, cold, y, workspace, stream);
-    return cat_tail_launch<bf16>(p, d, x, w, cold, y, workspace, stream);
+    const CatTailCold cold{x1, x2, wsc, bias, bias2, 0, 0, 0, 0};       // (the plan's half is filled in by the launch)
+    if (d->dtype == PWW_DTYPE_F16) return tail_launch<f16>("concat_convtail", p, x, w, cold, y, workspace, d->Cout, d->Cin, d->H, d->W, stream, d->C1, d->C2);
+    return tail_launch<bf16>("concat_convtail", p, x, w, cold, y, workspace, d->Cout, d->Cin, d->H, d->W, stream, d->C1, d->C2);
 }
 
 }  // namespace pww

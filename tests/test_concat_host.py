@@ -98,9 +98,10 @@ def test_the_plans_are_those_of_the_one_source_entry_points(lib, built_lib):
     gn_ws = lambda **kw: lib.pww_concat_group_norm_workspace_bytes(ctypes.byref(_gn(**kw)))  # noqa: E731
     assert gn_ws(HW=64) == 16 and gn_ws(HW=2304) == 2 * 14 * 8 * 16 and gn_ws(C1=1280, C2=1280, G=32, HW=576) == 2 * 64 * 32 * 16
     assert gn_ws(HW=35) == 0 and gn_ws(HW=4) == 0                                     # (as the one-source op: HW a multiple of 8)
-    # the twelve up-block resnets of SD1.5 at 2 rows, and small shapes: the same split (bytes = split * 4 M Cout)
+    # the twelve up-block resnets of SD1.5 at 2 rows, the two down-path shapes of the measured table (640 -> 1280 at 16 x 16, 320 -> 640 at
+    # 32 x 32: with them every row of TAIL_TUNED is reached through both entry points), and small shapes: the same split (bytes = split * 4 M Cout)
     for (C1, C2, Cout, side) in ((1280, 1280, 1280, 8), (1280, 1280, 1280, 16), (1280, 640, 1280, 16), (1280, 640, 640, 32), (640, 640, 640, 32), (640, 320, 640, 32),
-                                 (640, 320, 320, 64), (320, 320, 320, 64), (64, 128, 64, 8), (128, 64, 128, 8)):
+                                 (640, 320, 320, 64), (320, 320, 320, 64), (320, 320, 1280, 16), (256, 64, 640, 32), (64, 128, 64, 8), (128, 64, 128, 8)):
         for tile_n, splitk in ((0, 0), (64, 0), (0, 5)):
             one = _lib.ConvTailDesc(ctypes.sizeof(_lib.ConvTailDesc), 1, 2, side, side, Cout, C1 + C2, Cout, tile_n, splitk)
             two = _tail(H=side, W=side, Cin=Cout, C1=C1, C2=C2, Cout=Cout, tile_n=tile_n, splitk=splitk)

@@ -62,6 +62,20 @@ def test_header_exports_and_the_loader_entry(lib):
     assert "for name in pww_build.SIDE_LIBS_CONV" in entry
 
 
+def test_the_kernel_and_its_measured_table_exist_once():
+    """The conv2 + shortcut kernel and TAIL_TUNED are csrc/pww_shortcut_gemm.h and nowhere else: the one-source and the two-source unit
+    instantiate that header, neither carries a copy."""
+    import glob
+    csrc = os.path.join(REPO, "paint-with-words-sd_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) > 20
+    for text in ("TAIL_TUNED[]", "__launch_bounds__(CT_THREADS, 2)"):
+        holders = [os.path.basename(f) for f in files if text in open(f).read()]
+        assert holders == ["pww_shortcut_gemm.h"], (text, holders)
+    for unit in ("pww_conv_tail.hip", "pww_concat.hip"):
+        assert open(os.path.join(csrc, unit)).read().count('#include "pww_shortcut_gemm.h"') == 1, unit
+
+
 def test_a_missing_library_is_none_and_the_op_says_so(monkeypatch, tmp_path):
     from pww_hip import _lib
     monkeypatch.setitem(_lib._side, "convtail", None)

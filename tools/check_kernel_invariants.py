@@ -77,10 +77,11 @@ def check_linear(check):
 
 
 # (unit, main kernel, side-library flags): the three implicit-GEMM units of the 3 x 3 convolution
-# (pww_convwide.hip is pww_conv.hip compiled for the 160-wide tile alone: libpww_hip_convwide.so)
+# (pww_convwide.hip is pww_conv.hip compiled for the 160-wide tile alone: libpww_hip_convwide.so; pww_conv_tail.hip and pww_concat.hip
+# instantiate the one kernel of pww_shortcut_gemm.h, with one and with two sources of the shortcut's input)
 CONV_UNITS = [("pww_conv.hip", "conv3x3_kernel", [], (64, 128)), ("pww_convwide.hip", "conv3x3_kernel", ["-fvisibility=hidden"], (160,)),
-              ("pww_conv_tail.hip", "convtail_kernel", ["-fvisibility=hidden"], (64, 128, 160)),
-              ("pww_concat.hip", "cat_tail_kernel", ["-fvisibility=hidden"], (64, 128, 160))]
+              ("pww_conv_tail.hip", "shortcut_gemm_kernel", ["-fvisibility=hidden"], (64, 128, 160)),
+              ("pww_concat.hip", "shortcut_gemm_kernel", ["-fvisibility=hidden"], (64, 128, 160))]
 # tile width -> (VGPRs at most, waves per SIMD at least, MFMAs of the steady loop: 2 slabs x 2 k-steps x RN x 4)
 CONV_BUDGET = {64: (168, 3, 32), 128: (256, 2, 64), 160: (256, 2, 80)}
 
