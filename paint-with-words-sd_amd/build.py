@@ -30,6 +30,9 @@ Fifteen libraries come out of the same sources:
                                           with the padding on the right and bottom only) and the tail (norm, SiLU, conv to 8 channels, quant_conv, latent)
                                 text      the CLIP text encoder: the embedding gather with the first LayerNorm, the causal self-attention of at most
                                           128 tokens with head dim 64, and QuickGELU / GELU in place
+A sixteenth joins them, as a row of SIDE_LIBS_EXTRA in front of `text`:
+                                control   the residuals of a ControlNet: its 1 x 1 zero convolutions, the conditioning scale and the add into the
+                                          UNet's skip tensors as one grouped GEMM
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -76,6 +79,7 @@ SIDE_LIBS_EXTRA = {
     "vae": ("pww_vae.hip", [], "the AutoencoderKL decoder: one-head attention of head dim 512, and norm + SiLU + conv_out + image in two launches"),
     # (pww_conv.hip again: included with PWW_CONV_DOWN_UNIT, the downsampler's geometry on the 64- and 128-wide tiles)
     "vaeenc": ("pww_vaeenc.hip", ["pww_conv.hip"], "the AutoencoderKL encoder: image -> conv_in, the stride-2 downsamplers, and norm + SiLU + conv_out + quant_conv + latent in two launches"),
+    "control": ("pww_control.hip", [], "the residuals of a ControlNet: zero convolutions, conditioning scale and the add into the skips as one grouped GEMM"),
     "text": ("pww_text.hip", [], "the CLIP text encoder: embedding gather + LayerNorm, causal self-attention of head dim 64, QuickGELU / GELU"),
 }
 ALL_SIDE_LIBS = {**SIDE_LIBS, **SIDE_LIBS_CONV, **SIDE_LIBS_EXTRA}
@@ -93,6 +97,7 @@ LIB_CONVWIDE, CONVWIDE_UNITS = SIDE_PATHS["convwide"], SIDE_UNITS["convwide"]
 LIB_VAE, VAE_UNITS = SIDE_PATHS["vae"], SIDE_UNITS["vae"]
 LIB_VAEENC, VAEENC_UNITS = SIDE_PATHS["vaeenc"], SIDE_UNITS["vaeenc"]
 LIB_TEXT, TEXT_UNITS = SIDE_PATHS["text"], SIDE_UNITS["text"]
+LIB_CONTROL, CONTROL_UNITS = SIDE_PATHS["control"], SIDE_UNITS["control"]
 SIDE_PUBLIC_HEADERS = {"canvas": ["pww_hip_regions.h"]}       # include/ headers a side library's own header includes (besides pww_hip.h)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
@@ -185,6 +190,7 @@ def build_convwide(force=False, verbose=False): return build_side("convwide", fo
 def build_vae(force=False, verbose=False): return build_side("vae", force, verbose)  # noqa: E704
 def build_vaeenc(force=False, verbose=False): return build_side("vaeenc", force, verbose)  # noqa: E704
 def build_text(force=False, verbose=False): return build_side("text", force, verbose)  # noqa: E704
+def build_control(force=False, verbose=False): return build_side("control", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):

@@ -326,6 +326,73 @@ def _strength_maps(hold, color_map_images, device):
     return torch.stack(out, dim=0)
 
 
+CONTROL_MAX_NETS = 4      # ControlNets per call (pww_hip.controlnet.MAX_NETS)
+
+
+def _control_image_tensor(image, size):
+    """One control image -> float32 [3, H, W] in [0, 1]: a PIL image, a uint8 array [H, W, 3] (or [H, W]), or a float tensor [3, H, W] (or
+    [1, 3, H, W]) in [0, 1]. It must have the size of the color map, (width, height) = `size`."""
+    width, height = size
+    if torch.is_tensor(image):
+        t = image[0] if image.dim() == 4 and image.shape[0] == 1 else image
+        if t.dim() != 3 or t.shape[0] != 3 or not t.is_floating_point():
+            raise ValueError("control_image: a tensor must be a float [3, H, W] in [0, 1] (got %s %s)" % (tuple(image.shape), image.dtype))
+        if tuple(t.shape[1:]) != (height, width):
+            raise ValueError("control_image is %d x %d but the color map is %d x %d: they must have the same size" % (t.shape[2], t.shape[1], width, height))
+        t = t.detach().float().cpu()
+        if t.numel() and not (float(t.min()) >= 0.0 and float(t.max()) <= 1.0):
+            raise ValueError("control_image: a tensor must lie in [0, 1] (got %g .. %g)" % (float(t.min()), float(t.max())))
+        return t
+    if isinstance(image, Image.Image):
+        arr = np.array(image.convert("RGB"))
+    elif isinstance(image, np.ndarray):
+        arr = image
+    else:
+        raise ValueError("control_image must be a PIL image, a uint8 array or a float tensor in [0, 1] (got %s)" % type(image).__name__)
+    if arr.dtype != np.uint8 or arr.ndim not in (2, 3) or (arr.ndim == 3 and arr.shape[2] != 3):
+        raise ValueError("control_image: an array must be uint8 [H, W, 3] or [H, W] (got %s %s)" % (arr.shape, arr.dtype))
+    if arr.ndim == 2:
+        arr = np.repeat(arr[:, :, None], 3, axis=2)
+    if arr.shape[:2] != (height, width):
+        raise ValueError("control_image is %d x %d but the color map is %d x %d: they must have the same size" % (arr.shape[1], arr.shape[0], width, height))
+    return torch.from_numpy(np.ascontiguousarray(arr)).permute(2, 0, 1).float() / 255.0
+
+
+def _control_request(controlnet, control_image, scale, start, end, n, size):
+    """The `controlnet` / `control_image` / `controlnet_conditioning_scale` / `control_guidance_start` / `control_guidance_end` keywords of a
+    call of n images whose color maps are `size` -> None (no ControlNet) or the sampler's pww_hip.controlnet.ControlRequest. One net takes one
+    image (for every image of the call) or a list of n; a list of nets takes a list with such an entry per net."""
+    if controlnet is None:
+        if control_image is not None:
+            raise ValueError("control_image without a controlnet")
+        return None
+    many = isinstance(controlnet, (list, tuple))
+    nets = list(controlnet) if many else [controlnet]
+    if not 1 <= len(nets) <= CONTROL_MAX_NETS:
+        raise ValueError("controlnet: %d nets (1 .. %d)" % (len(nets), CONTROL_MAX_NETS))
+    if control_image is None:
+        raise ValueError("controlnet needs a control_image")
+    if many and (not isinstance(control_image, (list, tuple)) or len(control_image) != len(nets)):
+        raise ValueError("controlnet: a list of %d nets takes a list of %d control images" % (len(nets), len(nets)))
+    images = []
+    for entry in (control_image if many else [control_image]):
+        rows = list(entry) if isinstance(entry, (list, tuple)) else [entry] * n
+        if len(rows) != n:
+            raise ValueError("control_image has %d entries for %d requests" % (len(rows), n))
+        made = {}
+        for r in rows:
+            if id(r) not in made:
+                made[id(r)] = _control_image_tensor(r, size)
+        images.append(torch.stack([made[id(r)] for r in rows], dim=0))
+    scales = list(scale) if isinstance(scale, (list, tuple)) else [scale] * len(nets)
+    if len(scales) != len(nets) or any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in scales):
+        raise ValueError("controlnet_conditioning_scale must be a number or one per net (got %r for %d nets)" % (scale, len(nets)))
+    for v in (start, end):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError("control_guidance_start / control_guidance_end must be numbers in [0, 1] (got %r, %r)" % (start, end))
+    return pww_hip.controlnet.ControlRequest(nets, images, scales, start, end)
+
+
 def _txt2img_or_img2img(sizes, init_images, strength):
     """-> the (`start`, `strength`) arguments of _generate for a face that takes optional init images."""
     if init_images is None:
@@ -336,7 +403,7 @@ def _txt2img_or_img2img(sizes, init_images, strength):
 def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
               unconditional_input_prompt, start, strength=None, map_sizes=None, on_step=None, use_region_sigma=True, shared=False,
               max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0, region_prompts=None, region_base_weight=0.0,
-              region_feather=0.0, loras=None, canvas=None, hold=None):
+              region_feather=0.0, loras=None, canvas=None, hold=None, control=None):
     """The body behind every face of the package (reference :414-506, paint_with_words_inpaint.py:160-262): conditioning per request (once
     if `shared`: every request has the same map, context and prompt), the timesteps, the initial state, one denoise loop over all images.
     Returns the final latents [n, 4, h, w].
@@ -349,7 +416,8 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
     `lora` / `region_loras` keywords. canvas: None, or the plan of ONE request whose color map is larger than the UNet's window
     (_canvas_request): the conditioning is formed per window on the crop of the map, the initial state at canvas size. hold: None, or the
     region strengths of an img2img call (_hold_request): `start` is then _held_images, the request runs the schedule from hold["first"], and
-    the sampler is handed the init latents, the noise and one strength map per request (at canvas size for a canvas request)."""
+    the sampler is handed the init latents, the noise and one strength map per request (at canvas size for a canvas request). control: None,
+    or the ControlNets of the call (_control_request), handed to the sampler as they are."""
     unet, text_encoder, tokenizer, scheduler = tools[1:]
     n = len(seeds)
     if hold is not None:
@@ -406,6 +474,8 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
                         "first": hold["first"]}
     if canvas is not None:
         more["canvas"] = canvas
+    if control is not None:
+        more["control"] = control
     if loras is not None:
         rows = n if canvas is None else n_w         # (the rows of a canvas request are its windows: the one request's adapters for each of them)
         colors = [[e[0] for e in region_entries(r)] for r in region_prompts] if region_prompts else [[]] * n
@@ -456,6 +526,11 @@ def paint_with_words(
     canvas_window: Optional[int] = None,
     canvas_stride: Optional[int] = None,
     canvas_ramp: int = 0,
+    controlnet=None,
+    control_image=None,
+    controlnet_conditioning_scale=1.0,
+    control_guidance_start: float = 0.0,
+    control_guidance_end: float = 1.0,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -506,7 +581,16 @@ def paint_with_words(
     for bit; if every named strength equals `strength` the result is the plain img2img call's. It composes with negative regions, region
     prompts, LoRA adapters, long prompts and canvases (the strength map is then formed at canvas size). None / {} is the call without the
     feature. ValueError: no init_image, a strength outside [0, 1], more than 8 colours, a colour named twice, a feather outside [0, 8], a
-    color map that is not 8 x the latent, strengths that release nothing in T steps, a scheduler with steps_offset or without add_noise."""
+    color map that is not 8 x the latent, strengths that release nothing in T steps, a scheduler with steps_offset or without add_noise.
+    `controlnet` / `control_image` / `controlnet_conditioning_scale` / `control_guidance_start` / `control_guidance_end` (extension; the
+    reference's README chapter "Paint with Words + ControlNet"): a ControlNet -- or a list of at most 4 -- beside the color map: the control
+    image (scribble, depth, segmentation ...) steers the geometry, the color map which word goes where. control_image: a PIL image, a uint8
+    array or a float tensor in [0, 1] of the color map's size (a list of nets takes a list of images); the scale: a number or one per net;
+    the ControlNets act on the steps i of T with control_guidance_start <= i / T and (i + 1) / T <= control_guidance_end. A net must have the
+    layout pww_hip.controlnet.covers takes, in float16 / bfloat16 on the UNet's device. txt2img and img2img, every mode; it composes with
+    negative regions, region prompts, LoRA adapters (which act on the UNet alone), long prompts and region strength. Scale 0, or an empty
+    window, is the call without a ControlNet. ValueError: an image of another size, together with canvas_window. Not part of this: the
+    inpaint functions (a 9-channel UNet has no 4-channel ControlNet), the pipeline classes, pww_hip.dist."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context)
@@ -514,12 +598,17 @@ def paint_with_words(
     loras = check_loras(lora, region_loras, region_prompts, tools=preloaded_utils)
     color_map_image.size     # the reference dereferences it unconditionally (:414): None raises here too
     canvas = _canvas_request(color_map_image.size, canvas_window, canvas_stride, canvas_ramp)
+    if controlnet is not None and canvas_window is not None:
+        raise ValueError("controlnet does not combine with canvas_window (the hint would have to be cropped per window)")
+    control = _control_request(controlnet, control_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end, 1, color_map_image.size)
     hold = _hold_request(held, region_strength_feather, strength, num_inference_steps, [color_map_image], [init_image])
     tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
     start, strength = _txt2img_or_img2img([color_map_image.size], None if init_image is None else [init_image], strength)
     more = {} if canvas is None else {"canvas": canvas}
     if hold is not None:      # (a call without region strengths is, argument for argument, the call of before)
         start, more["hold"] = partial(_held_images, init_images=[init_image]), hold
+    if control is not None:   # (and so is a call without a ControlNet)
+        more["control"] = control
     latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps, guidance_scale,
                         weight_function, unconditional_input_prompt, start, strength, shared=True, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=[negative_color_context], negative_strength=negative_strength,
@@ -554,6 +643,11 @@ def paint_with_words_batch(
     region_strength_feather: float = 0.0,
     lora=None,
     region_loras=None,
+    controlnet=None,
+    control_image=None,
+    controlnet_conditioning_scale=1.0,
+    control_guidance_start: float = 0.0,
+    control_guidance_end: float = 1.0,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -572,7 +666,9 @@ def paint_with_words_batch(
     see paint_with_words; one dict for all requests or one per seed, every request with the same number of regions. lora / region_loras: see
     paint_with_words; `lora` serves every request, region_loras is one dict for all requests or one (or None) per seed. region_strength /
     region_strength_feather: see paint_with_words; one dict for all requests or one (or None) per seed -- all requests run the same steps:
-    from the step that releases the largest strength any of them names."""
+    from the step that releases the largest strength any of them names. controlnet / control_image / controlnet_conditioning_scale /
+    control_guidance_start / control_guidance_end: see paint_with_words; control_image is one image for all requests or one per seed (with a
+    list of nets: a list with such an entry per net)."""
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     seeds = list(seeds)
@@ -589,11 +685,14 @@ def paint_with_words_batch(
         raise ValueError("paint_with_words_batch: all color maps of one call must have the same size, got %s"
                          % sorted({m.size for m in maps}))
     hold = _hold_request(held, region_strength_feather, strength, num_inference_steps, maps, inits or [])
+    control = _control_request(controlnet, control_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end, n, maps[0].size)
     tools = _tools(preloaded_utils, device, scheduler_type, local_model_path, hf_model_path, model_token)
     start, strength = _txt2img_or_img2img([m.size for m in maps], inits, strength)
     more = {}
     if hold is not None:      # (a call without region strengths is, argument for argument, the call of before)
         start, more["hold"] = partial(_held_images, init_images=inits), hold
+    if control is not None:   # (and so is a call without a ControlNet)
+        more["control"] = control
     latents = _generate(tools, device, ctxs, maps, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
                         unconditional_input_prompt, start, strength, shared=shared, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=negs, negative_strength=negative_strength, region_prompts=_region_requests(region_prompts, n),

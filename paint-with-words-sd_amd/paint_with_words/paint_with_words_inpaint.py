@@ -132,6 +132,13 @@ def _inpaint_start(tools, device, seeds, timesteps, seeds_info, init_images, mas
     return latents, extra
 
 
+def _no_controlnet(controlnet, control_image):
+    """The inpaint functions carry the keywords only to answer them: their UNet reads 9 channels and a ControlNet reads the latent's 4."""
+    if controlnet is not None or control_image is not None:
+        raise ValueError("controlnet / control_image are not part of the inpaint functions: a 9-channel inpainting UNet has no 4-channel ControlNet "
+                         "(use paint_with_words or paint_with_words_batch)")
+
+
 @torch.no_grad()
 def paint_with_words_inpaint(
     color_context: Dict[Tuple[int, int, int], str] = {},
@@ -156,15 +163,18 @@ def paint_with_words_inpaint(
     negative_strength: float = 1.0,
     lora=None,
     region_loras=None,
+    controlnet=None,
+    control_image=None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
     max_prompt_chunks: int = 1,
 ):
     """reference :137-270. negative_color_context / negative_strength / region_prompts / region_base_weight / region_feather /
-    max_prompt_chunks / lora / region_loras (extensions): see paint_with_words. The region masks are read from the color map resized to the init image: its size
+    max_prompt_chunks / lora / region_loras (extensions): see paint_with_words; controlnet / control_image are refused (ValueError). The region masks are read from the color map resized to the init image: its size
     must be 8 x the latent's (a multiple of 32)."""
     check_prompt_chunks(max_prompt_chunks)
+    _no_controlnet(controlnet, control_image)
     check_negative_context(negative_color_context, negative_strength)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context)
     loras = check_loras(lora, region_loras, region_prompts, tools=preloaded_utils)
@@ -203,6 +213,8 @@ def paint_with_words_inpaint_batch(
     negative_strength: float = 1.0,
     lora=None,
     region_loras=None,
+    controlnet=None,
+    control_image=None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -213,6 +225,7 @@ def paint_with_words_inpaint_batch(
     have the same size. Image i equals the single-request call on request i. negative_color_context / negative_strength /
     region_prompts / region_base_weight / region_feather / max_prompt_chunks / lora / region_loras: see paint_with_words_batch."""
     check_prompt_chunks(max_prompt_chunks)
+    _no_controlnet(controlnet, control_image)
     check_negative_context(negative_color_context, negative_strength)
     seeds = list(seeds)
     n = len(seeds)

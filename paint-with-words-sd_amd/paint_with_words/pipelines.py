@@ -65,6 +65,8 @@ class PaintWithWord_StableDiffusionPipeline:
     # same reason. The inpaint class does not take them.
     region_strength = None
     region_strength_feather = 0.0
+    # ControlNets (see paint_with_words) are not part of the pipeline classes: setting `pipe.controlnet` is answered with a ValueError.
+    controlnet = None
 
     def __init__(self, vae, text_encoder, tokenizer, unet, scheduler=None, safety_checker=None, feature_extractor=None,
                  requires_safety_checker: bool = False):
@@ -108,6 +110,8 @@ class PaintWithWord_StableDiffusionPipeline:
         return (size or 64) * self.vae_scale_factor
 
     def _check_extensions(self):
+        if self.controlnet is not None:
+            raise ValueError("controlnet is not part of the pipeline classes (use paint_with_words or paint_with_words_batch)")
         check_prompt_chunks(self.max_prompt_chunks)
         check_negative_context(self.negative_color_context, self.negative_strength)
         check_region_prompts(self.region_prompts, self.region_base_weight, self.region_feather, self.negative_color_context)

@@ -5,6 +5,7 @@ from ._lib import PwwHipError, load as load_library, device_arch, LIB_PATH, EXPO
 from . import ops
 from . import blocks
 from . import lora
+from . import controlnet
 from .attention import QKProxy, ScaledW, inj_forward, install, uninstall, PwWAttnProcessor, pww_attention
 from .attnmaps import record_attention_maps, AttentionMaps
 

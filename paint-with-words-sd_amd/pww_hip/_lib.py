@@ -49,6 +49,9 @@ VAEENC_LIB_PATH = os.environ.get("PWW_HIP_VAEENC_LIB", os.path.join(_HERE, "libp
 #   text      the CLIP text encoder: the embedding gather with layer 0's first LayerNorm, the causal self-attention of at most 128 tokens with
 #             head dim 64, and QuickGELU / GELU in place (include/pww_hip_text.h): pww_hip.text_encode. Its spec is in SIDE_EXTRA below.
 TEXT_LIB_PATH = os.environ.get("PWW_HIP_TEXT_LIB", os.path.join(_HERE, "libpww_hip_text.so"))
+#   control   the residuals of a ControlNet: its 1 x 1 zero convolutions, the conditioning scale and the add into the UNet's skip tensors and
+#             mid-block output as ONE grouped GEMM (include/pww_hip_control.h): ops.control_residuals. Its spec is in SIDE_EXTRA below.
+CONTROL_LIB_PATH = os.environ.get("PWW_HIP_CONTROL_LIB", os.path.join(_HERE, "libpww_hip_control.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -152,6 +155,12 @@ TEXT_EXPORTS = ("pww_text_version", "pww_text_last_error", "pww_text_embed_ln", 
 TEXT_MIN_VERSION = 100
 TEXT_HEAD_DIM, TEXT_MAX_TOKENS, TEXT_MAX_WIDTH = 64, 128, 4096      # PWW_TEXT_* of the header
 TEXT_ACT_QUICK_GELU, TEXT_ACT_GELU = 0, 1
+
+
+# every symbol include/pww_hip_control.h declares for libpww_hip_control.so
+CONTROL_EXPORTS = ("pww_control_version", "pww_control_last_error", "pww_control_fwd", "pww_control_plan")
+CONTROL_MIN_VERSION = 100
+CONTROL_MAX_PROBLEMS, CONTROL_TILE_M, CONTROL_TILE_N = 16, 128, 64      # PWW_CONTROL_* of the header
 
 
 class AttnDesc(ctypes.Structure):
@@ -265,6 +274,18 @@ class VaeEncTailDesc(ctypes.Structure):
     """struct pww_vaeenc_tail_desc (GroupNorm + SiLU + conv to 8 channels + quant_conv + latent; size-prefixed)."""
     _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
                 ("C", ctypes.c_int32), ("eps", ctypes.c_float), ("scale", ctypes.c_float)]
+
+
+class ControlProblem(ctypes.Structure):
+    """struct pww_control_problem (one GEMM of the grouped launch: a zero convolution, its skip and its output)."""
+    _fields_ = [("h", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("skip", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("_pad", ctypes.c_int32),
+                ("h_stride", ctypes.c_int64), ("skip_stride", ctypes.c_int64), ("out_stride", ctypes.c_int64)]
+
+
+class ControlDesc(ctypes.Structure):
+    """struct pww_control_desc (the grouped launch; size-prefixed)."""
+    _fields_ = [("size", ctypes.c_uint32), ("dtype", ctypes.c_int32), ("n", ctypes.c_int32), ("scale_index", ctypes.c_int32)]
 
 
 class Region(ctypes.Structure):
@@ -491,6 +512,10 @@ SIDE_EXTRA = {
         "pww_vaeenc_tail_chunks": ([_P(VaeEncTailDesc)], _int),
         "pww_vaeenc_tail_stats": ([_vp, _vp, _P(VaeEncTailDesc), _vp, _sz, _vp], _int),
         "pww_vaeenc_tail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(VaeEncTailDesc), _vp, _sz, _vp], _int)}),
+    # missing_ok: the stock route (the zero convolutions as modules, a multiplication by the scale word, the adds) computes the same thing
+    "control": dict(path="CONTROL_LIB_PATH", exports=CONTROL_EXPORTS, min_version=CONTROL_MIN_VERSION, missing_ok=True, needs="the grouped ControlNet residual launch needs it", sigs={
+        "pww_control_fwd": ([_P(ControlProblem), _P(ControlDesc), _vp, _vp], _int),
+        "pww_control_plan": ([_P(ControlProblem), _i32, _P(_i32), _i32], _int)}),
     # required where the route runs (pww_hip/text_encode.py): PWW_TEXT_EMBED=0 / _ATTN=0 / _ACT=0 choose the stock sequences, a missing file does not
     "text": dict(path="TEXT_LIB_PATH", exports=TEXT_EXPORTS, min_version=TEXT_MIN_VERSION, missing_ok=False, needs="the CLIP text encoder's embedding, attention and activation need it", sigs={
         "pww_text_embed_ln": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp], _int),
@@ -605,6 +630,11 @@ def load_vaeenc():
 def load_text():
     lib = _side.get("text")
     return lib if lib is not None else load_side("text")
+
+
+def load_control():
+    lib = _side.get("control")
+    return lib if lib is not None else load_side("control")
 
 
 class experiments:

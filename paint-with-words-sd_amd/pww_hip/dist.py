@@ -195,7 +195,9 @@ def broadcast_request(payload, device, src=0, group=None):
     """Broadcast a request from `src`: every numpy array in the payload dict (the uint8 color map 'rgb', and for
     inpainting the mask and the init image) travels as a tensor broadcast, everything else (color_context, prompt, the
     negative context and its strength ...) pickled in one byte tensor. payload on src: dict; None elsewhere.
-    Returns the dict on every rank."""
+    Returns the dict on every rank. A request with a ControlNet is refused (ValueError): the nets and their hints are not distributed."""
+    if payload is not None and any(k in payload for k in ("controlnet", "control_image")):
+        raise ValueError("pww_hip.dist: a request with a controlnet / control_image is not supported (the ControlNets are not distributed)")
     if not (dist.is_available() and dist.is_initialized()):
         return payload
     rank = dist.get_rank()       # global, like `src`

@@ -1523,3 +1523,119 @@ def lora_update(y, x, layer_stack, state, n_seg):
                    "pww_lora_fwd", lib)
     _lora._stats["kernel"] += 1
     return y
+
+
+# ---- the residuals of a ControlNet as one grouped GEMM (csrc/pww_control.hip, libpww_hip_control.so) -------------------------------------
+CONTROL_MAX_PROBLEMS = _lib.CONTROL_MAX_PROBLEMS
+CONTROL_LAUNCHES = [0, 0]           # grouped launches, problems they held (pww_hip.controlnet.stats() reports them)
+
+
+def _nhwc_rows(t):
+    """A [B, C, H, W] float16 / bfloat16 tensor as the [B H W, C] rows of its channels_last memory: (rows, C, row pitch), or None when the
+    channels are not adjacent, the pixels do not follow each other at ONE pitch (a slice of the channels of a wider channels_last tensor
+    does), the pitch is no multiple of 8 elements or the first element is not 16-byte aligned. Nothing is copied."""
+    if not torch.is_tensor(t) or t.dim() != 4 or t.dtype not in _DT or t.data_ptr() % 16 or t.numel() == 0:
+        return None
+    B, C, H, W = t.shape
+    if C > 1 and t.stride(1) != 1:
+        return None
+    pitch = exp = None
+    for size, stride in ((W, t.stride(3)), (H, t.stride(2)), (B, t.stride(0))):
+        if size == 1:
+            continue
+        if pitch is None:
+            pitch, exp = stride, stride * size
+        elif stride != exp:
+            return None
+        else:
+            exp *= size
+    pitch = C if pitch is None else pitch
+    return None if pitch % 8 or pitch < C else (B * H * W, C, pitch)
+
+
+def _control_why_not(hs, convs, scale_word, skips=None, outs=None):
+    """None when pww_control_fwd runs this call, else the reason it would not (one line, for controlnet.stats())."""
+    n = len(hs)
+    if not 1 <= n <= CONTROL_MAX_PROBLEMS or len(convs) != n:
+        return "%d hidden states for %d zero convolutions (1 .. %d of each)" % (n, len(convs), CONTROL_MAX_PROBLEMS)
+    if not (torch.is_tensor(scale_word) and scale_word.is_cuda and scale_word.dtype == torch.float32 and scale_word.numel() >= 1 and scale_word.data_ptr() % 4 == 0):
+        return "the scale word must be a float32 tensor on the device"
+    dt = hs[0].dtype if torch.is_tensor(hs[0]) else None
+    for name, seq in (("skips", skips), ("outs", outs)):
+        if seq is not None and len(seq) != n:
+            return "%d %s for %d hidden states" % (len(seq), name, n)
+    for p, (h, conv) in enumerate(zip(hs, convs)):
+        w, b = getattr(conv, "weight", None), getattr(conv, "bias", None)
+        if not (torch.is_tensor(h) and h.is_cuda and h.dtype in _DT and h.dtype == dt and h.device == scale_word.device):
+            return "hidden state %d is not a float16 / bfloat16 tensor of one dtype on the scale word's device" % p
+        rows = _nhwc_rows(h)
+        if rows is None:
+            return "hidden state %d is not a channels_last [B, C, H, W] tensor with one row pitch (a multiple of 8), 16-byte aligned" % p
+        M, K, _ = rows
+        wv = _linear_weight(w) if torch.is_tensor(w) and w.is_cuda and w.dtype == dt and w.dim() == 4 else None
+        if wv is None or wv.shape[1] != K:
+            return "zero convolution %d is not a dense 1 x 1 weight of the hidden state's dtype and channels" % p
+        N = wv.shape[0]
+        if K % 64 or N % 64:
+            return "problem %d: K = %d and N = %d must be multiples of 64" % (p, K, N)
+        if not (torch.is_tensor(b) and b.is_cuda and b.dtype == dt and tuple(b.shape) == (N,) and b.is_contiguous() and b.data_ptr() % 8 == 0):
+            return "zero convolution %d has no dense, 8-byte aligned bias of its dtype" % p
+        if M * rows[2] >= 2 ** 31 or N * K >= 2 ** 31:
+            return "problem %d: tensor of 2^31 elements or more" % p
+        for name, seq in (("skip", skips), ("out", outs)):
+            t = None if seq is None else seq[p]
+            if t is None:
+                continue
+            r = _nhwc_rows(t) if torch.is_tensor(t) and t.is_cuda and t.dtype == dt else None
+            if r is None or tuple(t.shape) != (h.shape[0], N) + tuple(h.shape[2:]) or M * r[2] >= 2 ** 31:
+                return "%s %d is not a channels_last [B, %d, H, W] tensor of the hidden state's dtype and size with one row pitch" % (name, p, N)
+    return None
+
+
+def control_takes(hs, convs, scale_word, skips=None, outs=None):
+    """True when ops.control_residuals runs this call on the grouped kernel -- everything the library would answer PWW_ENOTSUP or PWW_EINVAL
+    to is declined here, and so is a missing libpww_hip_control.so: 1 .. 16 channels_last [B, C, H, W] float16 / bfloat16 hidden states on a
+    HIP device, taken as their [B H W, C] rows (one pitch, a multiple of 8 elements, 16-byte aligned), as many plain 1 x 1 nn.Conv2d (dense
+    weight and bias of that dtype, channel counts multiples of 64), a float32 scale word on the device; where given, skips / outs of the
+    outputs' shape with one row pitch too (an entry may be None)."""
+    return _control_why_not(hs, convs, scale_word, skips, outs) is None and _lib.load_control() is not None
+
+
+def control_residuals(hs, convs, scale_word, skips=None, outs=None):
+    """out_p = T(skip_p + s * conv_p(h_p)) for every p (skips None, or an entry None: T(s * conv_p(h_p))), s = scale_word[0] as the device
+    holds it when the launch RUNS -- a captured graph follows the word. ONE launch for all problems, fp32 accumulation, one rounding at the
+    store; s == 0 returns the skips bit for bit. hs / skips / outs: [B, C, H, W] channels_last tensors read and written in place as their
+    [B H W, C] rows (nothing is copied); convs: the 1 x 1 nn.Conv2d modules, weights used in place. outs default to new channels_last tensors
+    (an out may be its skip). Returns the list of outs. Raises where control_takes declines."""
+    _require_gpu(*[t for t in hs if torch.is_tensor(t)])
+    why = _control_why_not(hs, convs, scale_word, skips, outs)
+    if why is not None:
+        raise PwwHipError("control_residuals: " + why)
+    lib = _lib.load_control()
+    if lib is None:
+        raise PwwHipError("control_residuals: libpww_hip_control.so is not built " + _lib._HINT)
+    n = len(hs)
+    table = (_lib.ControlProblem * n)()
+    result = []
+    for p, (h, conv) in enumerate(zip(hs, convs)):
+        M, K, hp = _nhwc_rows(h)
+        N = conv.weight.shape[0]
+        skip = None if skips is None else skips[p]
+        out = None if outs is None else outs[p]
+        if out is None:
+            out = torch.empty((h.shape[0], N) + tuple(h.shape[2:]), dtype=h.dtype, device=h.device, memory_format=torch.channels_last)
+            if _nhwc_rows(out) is None:        # (a one-pixel tensor's strides are the allocator's choice: make the rows explicit)
+                out = torch.empty((M, N), dtype=h.dtype, device=h.device).view(h.shape[0], h.shape[2], h.shape[3], N).permute(0, 3, 1, 2)
+        e = table[p]
+        e.h, e.w, e.bias, e.out = h.data_ptr(), conv.weight.data_ptr(), conv.bias.data_ptr(), out.data_ptr()
+        e.skip = skip.data_ptr() if skip is not None else None
+        e.M, e.N, e.K = M, N, K
+        e.h_stride, e.out_stride = hp, _nhwc_rows(out)[2]
+        e.skip_stride = _nhwc_rows(skip)[2] if skip is not None else 0
+        result.append(out)
+    d = _lib.ControlDesc(ctypes.sizeof(_lib.ControlDesc), _DT[hs[0].dtype], n, 0)
+    with torch.cuda.device(hs[0].device):
+        _lib.check(lib.pww_control_fwd(table, ctypes.byref(d), _ptr(scale_word), _stream()), "pww_control_fwd", lib)
+    CONTROL_LAUNCHES[0] += 1
+    CONTROL_LAUNCHES[1] += n
+    return result

@@ -26,6 +26,11 @@ on the canvas.
 Region strength (`hold=`, img2img; Differential Diffusion): every latent pixel has a strength S in [0, 1] and is released to the loop at the
 step its strength allows (hold_thresholds); one launch behind every scheduler.step (ops.hold_apply, outside the captured graph) puts the
 pixels that the next step does not release back to the init latent noised to that step's timestep.
+ControlNets (`control=`, a controlnet.ControlRequest): every evaluation of the UNet goes through a controlnet.ControlledUNet instead -- the
+ControlNet's encoder on the same rows, then one grouped launch per net that scales its thirteen zero convolutions and adds them into the UNet's
+skip tensors. The hint (the embedded control image) lives in a static tensor, one row per UNet row; the conditioning scale in a device word
+that is rewritten before every evaluation: 0 outside the guidance window, where "eager" and "folded" skip the ControlNet and "graph" replays
+its ONE graph with the word at 0.
 """
 import numpy as np
 import torch
@@ -33,6 +38,7 @@ import torch
 from . import ops
 from . import attnmaps
 from . import lora as _lora
+from . import controlnet as _controlnet
 from .attention import install, refresh_kv_cache, refresh_orig_cache, ROW_GATE, KV_CACHE, COEFF_SLOTS, CoeffSlots, COMPACT_W, COMPACT_IDX, GATED_ROWS, COND_ROWS, BIAS_COLS, ATTN_RECORDER
 from .conditioning import PwWContext
 
@@ -385,6 +391,8 @@ class _GraphedUNet:
             self.captures += 1
         g, out, trace = entry
         g.replay()
+        if hasattr(self.unet, "replayed"):
+            self.unet.replayed()      # a ControlledUNet's tally of the launches the replay ran again
         if rec is not None and trace:
             rec.replayed(trace)       # the host's tally of what the replay added to each accumulator
         return out
@@ -407,11 +415,12 @@ class PwWSampler:
         self._scratch_modules = None
         self._errors = ops.FusedErrorWatch()
         self._lora = None                # the UNet's lora.LoraState while adapters are loaded (looked up per request)
+        self._controlled = {}            # (ids of the nets) -> the controlnet.ControlledUNet of this UNet with them
         self._lora_calls = None          # eager mode: the one-row assignment of every batch-1 call of the request, [class * n + image]
         self.handoff_pending = False     # the last request issued launches with an in-kernel hand-off (PWW_QPROJ_STAT=0 / shapes the
                                          # to_q GEMM does not cover): its latents must not reach a caller before check_errors() has looked
 
-    def _static_context(self, folded, weight_function, latents, timesteps, rec=None, batch_shape=None):
+    def _static_context(self, folded, weight_function, latents, timesteps, rec=None, batch_shape=None, control=None):
         """Captured graphs read the context tensors by ADDRESS: keep one set of static tensors alive and copy each new
         request's values into them; rebuild the graphs when the geometry changes. The weight function and the schedule are
         NOT part of the key while the function's scalars travel in device words (CoeffSlots) -- fresh lambdas, other
@@ -424,6 +433,8 @@ class PwWSampler:
                None if rec is None else ("attention maps", rec.per_layer))
         if self._lora is not None:      # LoRA launches are part of the graph: with which padded rank, over which stacks -- not for which rows
             sig = sig + (self._lora.signature(),)
+        if control is not None:         # the ControlNets' launches are part of the graph: which nets, the hints' shapes, which route -- not the image, scale or window
+            sig = sig + (control.signature(),)
         self._request_folded = folded
         if sig != self._graph_sig:
             self._graphed.reset()
@@ -527,7 +538,7 @@ class PwWSampler:
 
     @torch.no_grad()
     def sample(self, cond, uncond, latents, timesteps, guidance_scale, weight_function, extra_channels=None,
-               on_step=None, negative_strength=1.0, regions=None, lora_rows=None, canvas=None, hold=None):
+               on_step=None, negative_strength=1.0, regions=None, lora_rows=None, canvas=None, hold=None, control=None):
         """cond / uncond: the two context dicts of the PwW protocol, or one dict per image (per-image prompts / maps).
         regions: None, or the region prompts of the request -- one plan of conditioning.encode_region_prompts or one per image: K more rows
         per image, blended per latent pixel (ops.region_combine) where guidance is combined otherwise.
@@ -543,6 +554,8 @@ class PwWSampler:
         add_noise(x0, z, timesteps[0])); "strength": S fp32 [n, h, w] in [0, 1] (ops.hold_strength_map), at canvas size for a canvas
         request; "steps": T, "first": i0 -- `timesteps` are the steps i0 .. T - 1 of the T-step schedule}. Behind every scheduler.step, and in
         front of on_step, one launch (ops.hold_apply; outside the captured graph) holds the pixels the next step does not release.
+        control: None, or a controlnet.ControlRequest -- the ControlNets of the request with their control images (one row per image), conditioning
+        scales and guidance window. ValueError with a canvas and with extra_channels.
         extra_channels: inpaint's cat([mask, masked_image_latents]) ([n or 1, 5, h, w]) or None."""
         sch, unet, dev = self.scheduler, self.unet, latents.device
         self._errors.poll(wait=False)      # a hand-off time-out of an earlier request surfaces here (or in check_errors())
@@ -583,10 +596,27 @@ class PwWSampler:
                 d.setdefault(KV_CACHE, {}).clear()
         folded = None
         rec = attnmaps.active()        # pww_hip.record_attention_maps(): the recorder rides in the conditional context(s) of this request
+        model = None
+        if control is not None:
+            if canvas is not None:
+                raise ValueError("controlnet: a canvas larger than the window is not supported (the hint would have to be cropped per window)")
+            if extra_channels is not None:
+                raise ValueError("controlnet: extra UNet input channels (inpainting) are not supported")
+            key = tuple(id(net) for net in control.nets)
+            model = self._controlled.get(key)
+            if model is None:
+                model = self._controlled[key] = _controlnet.ControlledUNet(unet, control.nets)
+            # (before _static_context: the hints' shapes are part of the graph signature)
+            model.begin_request(control, n, 1 if self.mode == "eager" else (blend["K"] if blend else 0) + 2)
+        if self._graphed is not None:
+            self._graphed.unet = unet if model is None else model      # (what the next capture records; the signature below tells them apart)
+        more = {} if model is None else {"control": (control, model)}      # (a call without ControlNets is, argument for argument, the call of before)
         if self.mode != "eager":
             folded = _fold_context(cond, uncond, n, dev, negative_strength) if blend is None else _fold_regions(cond, regions, uncond, n, dev)
             if self._graphed is not None:
-                if canvas is None:
+                if model is not None:
+                    folded = self._static_context(folded, weight_function, latents, timesteps, rec, control=model)
+                elif canvas is None:
                     folded = self._static_context(folded, weight_function, latents, timesteps, rec)
                 else:
                     folded = self._static_context(folded, weight_function, latents, timesteps, rec, batch_shape=(n, latents.shape[1]) + frame)
@@ -597,7 +627,7 @@ class PwWSampler:
                                  hold=held)
         if rec is None:
             return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, None, negative_strength, blend,
-                                 hold=held)
+                                 hold=held, **more)
         static = self._static_maps if self._graphed is not None else None
         rec.begin_request(n, latents.shape[-2:], static=static)      # (hipGraph mode: zeroes the static accumulators, before the first replay)
         holders = conds if folded is None else [folded]
@@ -605,15 +635,15 @@ class PwWSampler:
             d[ATTN_RECORDER] = rec
         try:
             return self._denoise(conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength, blend,
-                                 hold=held)
+                                 hold=held, **more)
         finally:
             for d in holders:
                 d.pop(ATTN_RECORDER, None)
             rec.end_request(static=static is not None)
 
     def _denoise(self, conds, unconds, folded, latents, timesteps, guidance_scale, weight_function, extra_channels, on_step, rec, negative_strength=1.0, blend=None,
-                 canvas=None, hold=None):
-        """The loop of sample() (reference :470-506). blend: the region prompts of the request (sample()), or None. canvas: the plan of a
+                 canvas=None, hold=None, control=None):
+        """The loop of sample() (reference :470-506). control: None, or (the request, its ControlledUNet). blend: the region prompts of the request (sample()), or None. canvas: the plan of a
         canvas request, or None -- `latents` is then the canvas, and the n images of the UNet evaluation are its windows. hold: the region
         strengths of the request with their (theta, a, b) per step (_hold_table), or None."""
         sch, unet, n = self.scheduler, self.unet, latents.shape[0] if canvas is None else len(conds)
@@ -625,8 +655,19 @@ class PwWSampler:
         uncond_functions = [negative_function if _has_negative_maps(u) else zero_function for u in unconds] if folded is None else None
         K = blend["K"] if blend is not None else 0
         calls = self._lora_calls        # eager mode with LoRA adapters loaded: every batch-1 call has its own one-row assignment
+        plain_unet = unet
         for i, t in enumerate(timesteps):
             sigma, _ = self._sigma_and_index(i, t)
+            if control is not None:
+                # the scale words of this step: 0 outside the guidance window. "graph" replays its one graph with them; "eager" and "folded"
+                # run the ControlNets only where a word is not 0
+                words = control[0].words(i, len(timesteps))
+                live = any(w != 0.0 for w in words)
+                if self.mode == "graph" or live:
+                    control[1].set_words(words)
+                unet = control[1] if live else plain_unet
+                if not live and self.mode != "graph":
+                    _controlnet._STATS["skipped_steps"] += 1
             if canvas is None:
                 x = sch.scale_model_input(latents, t)
             else:
@@ -642,6 +683,8 @@ class PwWSampler:
                     conds[j].update({"SIGMA": sigma, "WEIGHT_FUNCTION": weight_function})
                     if rec is not None:
                         rec.row = j
+                    if control is not None:
+                        control[1].row = j      # the hint of a batch-1 call is its image's
                     if calls is not None:
                         self._lora_call(calls[j], conds[j], n)
                     eps_c.append(unet(x[j:j + 1], t, encoder_hidden_states=conds[j]).sample)
@@ -699,7 +742,7 @@ class PwWSampler:
         # did any fused cross-attention launch of this request time out in its hand-off? One 4-byte device -> host copy behind an
         # event (ops.FusedErrorWatch): looked at when the next request starts and by check_errors() -- never a host stall here
         if self._scratch_modules is None:
-            self._scratch_modules = [m for m in unet.modules() if m.__class__.__name__ in ("CrossAttention", "Attention")]
+            self._scratch_modules = [m for m in self.unet.modules() if m.__class__.__name__ in ("CrossAttention", "Attention")]
         self.handoff_pending = self._errors.post(self._scratch_modules)
         return latents
 

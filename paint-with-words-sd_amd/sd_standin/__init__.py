@@ -5,3 +5,4 @@ from .unet import (CrossAttention, BasicTransformerBlock, Transformer2DModel, UN
 from .schedulers import LMSDiscreteScheduler, PLMSScheduler
 from .text import HashTokenizer, TinyTextEncoder, CLIPTextEncoder, build_clip_text_encoder
 from .vae import TinyVAE, AutoencoderKL, AutoencoderKLEncDec, SD_VAE_CONFIG
+from .controlnet import ControlNetModel, ControlNetConditioningEmbedding, build_controlnet

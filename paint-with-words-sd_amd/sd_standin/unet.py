@@ -306,7 +306,9 @@ class UNet2DConditionModel(nn.Module):
     def device(self):
         return self.conv_in.weight.device
 
-    def forward(self, sample, timestep, encoder_hidden_states=None):
+    def forward(self, sample, timestep, encoder_hidden_states=None, down_block_additional_residuals=None, mid_block_additional_residual=None):
+        """down_block_additional_residuals / mid_block_additional_residual (diffusers' names): a ControlNet's residuals, added to the skip
+        tensors behind the down path and to the mid block's output; None (the default) runs the statements of the plain forward."""
         if not torch.is_tensor(timestep):
             timestep = torch.tensor([timestep], dtype=torch.float32, device=sample.device)
         timestep = timestep.to(sample.device).reshape(-1).expand(sample.shape[0])
@@ -318,7 +320,11 @@ class UNet2DConditionModel(nn.Module):
         for blk in self.down_blocks:
             x, outs = blk(x, temb, encoder_hidden_states)
             skips += outs
+        if down_block_additional_residuals is not None:
+            skips = tuple(s + r for s, r in zip(skips, down_block_additional_residuals))
         x = self.mid_block(x, temb, encoder_hidden_states)
+        if mid_block_additional_residual is not None:
+            x = x + mid_block_additional_residual
         for blk in self.up_blocks:
             x, skips = blk(x, skips, temb, encoder_hidden_states)
         x = self.conv_out(F.silu(self.conv_norm_out(x)))
