@@ -1,8 +1,9 @@
 """GPU tests of libpww_hip_concat.so (csrc/pww_concat.hip): GroupNorm and conv2 + shortcut reading the two halves of
 `torch.cat([x1, x2], 1)` where they lie, and the restated up block of pww_hip/blocks.py.
 
-The ONLY bar is torch.equal against the existing one-source op on the concatenated tensor: a concatenation copies and computes nothing,
-and the two-source kernels keep launch form, summation order, tile, K order and split of the one-source ones.
+The bar is torch.equal against the existing one-source op on the concatenated tensor: a concatenation copies and computes nothing,
+and the two-source kernels keep launch form, summation order, tile, K order and split of the one-source ones. One float16 GroupNorm case
+under a large mean is also held to norm_cases.reference: equality alone would not see a mistake that both copies of the kernels share.
 
 GroupNorm shapes. The launch form is chosen by shape (the two-source op asks the same selector for C1 + C2 channels), so each form is
 reached the way test_norm_edges_gpu.py reaches it, by a shape, and the form is asserted from the workspace size (16 bytes: one launch):
@@ -79,6 +80,52 @@ def test_group_norm_equals_the_one_source_op_on_the_concatenation(case, dtype):
         # a caller's workspace full of 0xFF (NaN partials wherever a kernel reads what it did not write): the same bits
         ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=DEV)
         assert torch.equal(ops.group_norm_cat(x1, x2, G, w, b, 1e-5, act="silu", workspace=ws), ops.group_norm(cat, G, w, b, 1e-5, act="silu"))
+
+
+# float16 under a large mean, the smallest shape of each launch form above: (C1, C2, groups) -> (H, W, form, nslab)
+STAT_CASES = {(64, 32, 8): (8, 8, "group", 1), (64, 32, 16): (16, 16, 256, 2), (1280, 1280, 32): (24, 24, 512, 64)}
+
+
+@pytest.mark.parametrize("case", list(STAT_CASES), ids=_ids)
+def test_group_norm_float16_statistics_under_a_large_mean(case):
+    """Every channel at mean 300 with a spread of 0.5, float16: where plain fp32 sums of float16 squares break (csrc/pww_norm.hip, header),
+    so the pivot of the two-source kernels -- in the two-launch forms handed to the fold through LDS -- has to be right. Two bars:
+      * torch.equal with ops.group_norm on the concatenation: this unit's own source select and pitch in front of the first load;
+      * norm_cases.reference (fp64 statistics, the kernel's rounding points): one rounding step, two behind SiLU, no element outside. The
+        kernels of csrc/pww_concat.hip are a copy of those of csrc/pww_norm.hip, and test_norm_edges_gpu.py holds the one-source op to the
+        reference under this mean at other shapes only: equality alone would pass a mistake both copies share at these.
+    No affine map and eps 1e-6, as in test_norm_edges_gpu.py's large-mean test: the output is (h - mean) * rstd, and the reference's own
+    fp32 `h * a + b` then rounds once at magnitude 600 (half a unit there, 3.1e-5, plus half a float16 spacing of the result, against the
+    bar's floor of 2^-10 * 1e-2 * max |ref| = 3.9e-5 at max |ref| = 4.0); with gamma and beta its b takes two more roundings of that size
+    and the reference would be looser than the bar.
+    On the CPU, at these inputs: the reference is finite (max |ref| 4.0 - 5.0). The stock sequence is within the bars behind SiLU (worst
+    0.62 - 0.86 of the tolerance) and NOT in front of it: with the norm in fp32 609 of 12 288, 1 853 of 49 152 and 163 127 of 2 949 120
+    elements lie outside one step (worst 1.8 - 2.0 tolerances), with the norm in fp64 still 0, 1 233 and 26 934 (worst 0.9 - 1.7), every one
+    of them at |ref| < 0.05, where the bar is its floor (3.9e-5) and every fp32 rounding at this mean is of the floor's size: the stock
+    op's fp32 statistics, and the fp32 mean (300) and b = -a * mean (600) that the reference shares with the kernels but not with the
+    stock op. So the stock sequence is no yardstick for outputs near zero in this regime; the bar against the reference stands as set."""
+    import norm_cases as N
+    from pww_hip import _lib
+    ops = _ops()
+    dtype = torch.float16
+    C1, C2, G = case
+    H, W, form, nslab = STAT_CASES[case]
+    C, B = C1 + C2, 2
+    g = torch.Generator().manual_seed(11 + C1 + 7 * C2 + G)
+    x = 300.0 + 0.5 * torch.randn(B, C, H, W, generator=g)
+    x1, x2 = _cl(x[:, :C1], dtype), _cl(x[:, C1:], dtype)
+    cat = torch.cat([x1, x2], dim=1).contiguous(memory_format=CL)
+    need = int(_lib.load_concat().pww_concat_group_norm_workspace_bytes(ctypes.byref(ops._gn_cat_desc(x1, x2, G, 1e-6, None))))
+    assert need == (16 if form == "group" else B * nslab * G * 16) and (C // 8 > 256) == (form == 512), (case, need)
+    for act in (None, "silu"):
+        got = ops.group_norm_cat(x1, x2, G, None, None, 1e-6, act=act)
+        want = ops.group_norm(cat, G, None, None, 1e-6, act=act)
+        ref = N.reference(cat, None, None, None, G, 1e-6, act, dtype)
+        nbad, rel = N.close(got, ref, dtype, steps=2 if act else 1)
+        print("large mean %s %dx%d %s act %s: equal %s, %d outside, max |diff| / max |ref| %.3e" % (case, H, W, form, act, torch.equal(got, want), nbad, rel))
+        assert torch.isfinite(ref.float()).all() and ref.float().abs().max() > 1.0
+        assert torch.equal(got, want), (case, act, int((got != want).sum()))
+        assert nbad == 0, (case, act, nbad, rel)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
