@@ -33,6 +33,9 @@ Fifteen libraries come out of the same sources:
 A sixteenth joins them, as a row of SIDE_LIBS_EXTRA in front of `text`:
                                 control   the residuals of a ControlNet: its 1 x 1 zero convolutions, the conditioning scale and the add into the
                                           UNet's skip tensors as one grouped GEMM
+and one more, as a row of SIDE_LIBS_EXTRA in front of `control`:
+                                step      one sampler step (Euler, Euler ancestral, DDIM, DPM-Solver++ 2M) as one elementwise launch: the guidance
+                                          combine, the scheduler's affine update, the history write and the next UNet input
 The large kernel families are instantiated in slices (one translation unit per storage type, the general cross-attention kernel also per
 workgroup width) so that the compile runs side by side on the build box's cores.
 """
@@ -79,6 +82,7 @@ SIDE_LIBS_EXTRA = {
     "vae": ("pww_vae.hip", [], "the AutoencoderKL decoder: one-head attention of head dim 512, and norm + SiLU + conv_out + image in two launches"),
     # (pww_conv.hip again: included with PWW_CONV_DOWN_UNIT, the downsampler's geometry on the 64- and 128-wide tiles)
     "vaeenc": ("pww_vaeenc.hip", ["pww_conv.hip"], "the AutoencoderKL encoder: image -> conv_in, the stride-2 downsamplers, and norm + SiLU + conv_out + quant_conv + latent in two launches"),
+    "step": ("pww_step.hip", [], "one sampler step as one launch: guidance combine, the scheduler's affine update, history and the next UNet input"),
     "control": ("pww_control.hip", [], "the residuals of a ControlNet: zero convolutions, conditioning scale and the add into the skips as one grouped GEMM"),
     "text": ("pww_text.hip", [], "the CLIP text encoder: embedding gather + LayerNorm, causal self-attention of head dim 64, QuickGELU / GELU"),
 }
@@ -98,6 +102,7 @@ LIB_VAE, VAE_UNITS = SIDE_PATHS["vae"], SIDE_UNITS["vae"]
 LIB_VAEENC, VAEENC_UNITS = SIDE_PATHS["vaeenc"], SIDE_UNITS["vaeenc"]
 LIB_TEXT, TEXT_UNITS = SIDE_PATHS["text"], SIDE_UNITS["text"]
 LIB_CONTROL, CONTROL_UNITS = SIDE_PATHS["control"], SIDE_UNITS["control"]
+LIB_STEP, STEP_UNITS = SIDE_PATHS["step"], SIDE_UNITS["step"]
 SIDE_PUBLIC_HEADERS = {"canvas": ["pww_hip_regions.h"]}       # include/ headers a side library's own header includes (besides pww_hip.h)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading SCALAR arguments of a kernel (<= 14 dwords: 16 user SGPRs less the kernarg pointer) are preloaded
@@ -107,9 +112,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall",
          "-Wno-unused-function", "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
-# pww_mask.hip, pww_regions.hip, pww_canvas.hip and pww_hold.hip restate fp32 formulas that must match a CPU restatement bit for bit: no FMA contraction.
+# pww_mask.hip, pww_regions.hip, pww_canvas.hip, pww_hold.hip and pww_step.hip restate fp32 formulas that must match a CPU restatement bit for bit: no FMA contraction.
 PER_FILE_FLAGS = {"pww_mask.hip": ["-ffp-contract=off"], "pww_regions.hip": ["-ffp-contract=off"], "pww_canvas.hip": ["-ffp-contract=off"],
-                  "pww_hold.hip": ["-ffp-contract=off"]}
+                  "pww_hold.hip": ["-ffp-contract=off"], "pww_step.hip": ["-ffp-contract=off"]}
 
 
 def _newer(target, deps):
@@ -191,6 +196,7 @@ def build_vae(force=False, verbose=False): return build_side("vae", force, verbo
 def build_vaeenc(force=False, verbose=False): return build_side("vaeenc", force, verbose)  # noqa: E704
 def build_text(force=False, verbose=False): return build_side("text", force, verbose)  # noqa: E704
 def build_control(force=False, verbose=False): return build_side("control", force, verbose)  # noqa: E704
+def build_step(force=False, verbose=False): return build_side("step", force, verbose)  # noqa: E704
 
 
 def _build_check(exe, lib, libname, defines, force):

@@ -142,6 +142,35 @@ def _sampler_for(unet, scheduler):
     return cache[key]
 
 
+# `sampler=` of the four function faces: name -> (class of sd_standin.schedulers, constructor keywords beside the betas and prediction_type)
+SAMPLERS = {
+    "euler": ("EulerDiscreteScheduler", {}),
+    "euler_karras": ("EulerDiscreteScheduler", {"use_karras_sigmas": True}),
+    "euler_a": ("EulerAncestralDiscreteScheduler", {}),
+    "ddim": ("DDIMScheduler", {}),
+    "dpmpp_2m": ("DPMSolverMultistepScheduler", {}),
+    "dpmpp_2m_karras": ("DPMSolverMultistepScheduler", {"use_karras_sigmas": True}),
+}
+
+
+def check_sampler(sampler):
+    """The `sampler` keyword, before any model is touched: None, or one of SAMPLERS' names (ValueError otherwise)."""
+    if sampler is not None and (not isinstance(sampler, str) or sampler not in SAMPLERS):
+        raise ValueError("sampler must be None or one of %s (got %r)" % (", ".join(sorted(SAMPLERS)), sampler))
+    return sampler
+
+
+def _named_scheduler(name, base):
+    """The scheduler a `sampler=` name stands for, with the betas and the prediction_type of `base` (the scheduler in the tools)."""
+    from sd_standin import schedulers
+    config = getattr(base, "config", None) or {}
+    get = config.get if hasattr(config, "get") else (lambda key, default=None: getattr(config, key, default))
+    cls, kw = SAMPLERS[name]
+    return getattr(schedulers, cls)(num_train_timesteps=get("num_train_timesteps", 1000), beta_start=get("beta_start", 0.00085),
+                                    beta_end=get("beta_end", 0.012), beta_schedule=get("beta_schedule", "scaled_linear"),
+                                    prediction_type=get("prediction_type", None) or "epsilon", **kw)
+
+
 def _broadcast(value, n, name):
     """A per-request argument of paint_with_words_batch: one value for every request, or a sequence of n."""
     if isinstance(value, (list, tuple)) and not (name == "color_context" and isinstance(value, dict)):
@@ -403,7 +432,7 @@ def _txt2img_or_img2img(sizes, init_images, strength):
 def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
               unconditional_input_prompt, start, strength=None, map_sizes=None, on_step=None, use_region_sigma=True, shared=False,
               max_prompt_chunks=1, negative_color_contexts=None, negative_strength=1.0, region_prompts=None, region_base_weight=0.0,
-              region_feather=0.0, loras=None, canvas=None, hold=None, control=None):
+              region_feather=0.0, loras=None, canvas=None, hold=None, control=None, sampler_name=None):
     """The body behind every face of the package (reference :414-506, paint_with_words_inpaint.py:160-262): conditioning per request (once
     if `shared`: every request has the same map, context and prompt), the timesteps, the initial state, one denoise loop over all images.
     Returns the final latents [n, 4, h, w].
@@ -417,12 +446,18 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
     (_canvas_request): the conditioning is formed per window on the crop of the map, the initial state at canvas size. hold: None, or the
     region strengths of an img2img call (_hold_request): `start` is then _held_images, the request runs the schedule from hold["first"], and
     the sampler is handed the init latents, the noise and one strength map per request (at canvas size for a canvas request). control: None,
-    or the ControlNets of the call (_control_request), handed to the sampler as they are."""
+    or the ControlNets of the call (_control_request), handed to the sampler as they are. sampler_name: None, or the `sampler` keyword of
+    the call (check_sampler): the request runs on that scheduler, built for this call from the tools' scheduler's config, on the tools'
+    PwWSampler -- so a captured graph serves every scheduler."""
     unet, text_encoder, tokenizer, scheduler = tools[1:]
     n = len(seeds)
+    base = scheduler
+    if sampler_name is not None:
+        scheduler = _named_scheduler(sampler_name, base)
+        tools = tuple(tools[:4]) + (scheduler,)
     if hold is not None:
         _hold_scheduler_check(scheduler)
-    sampler = _sampler_for(unet, scheduler)   # also installs the attention plug
+    sampler = _sampler_for(unet, base)   # also installs the attention plug
     conds, unconds, seeds_info = [], [], []
     region_texts = [e[1] for r in (region_prompts or []) for e in region_entries(r)]
     min_chunks = _batch_prompt_chunks(tokenizer, (prompts[:1] if shared else prompts) + [unconditional_input_prompt] + region_texts, max_prompt_chunks)
@@ -482,8 +517,15 @@ def _generate(tools, device, color_contexts, color_map_images, prompts, seeds, n
         region_loras = loras[1] if canvas is None or loras[1] is None else list(loras[1]) * n_w
         more["lora_rows"] = pww_hip.lora.row_plan(rows, colors if canvas is None else colors * n_w, loras[0], region_loras, pww_hip.lora.state_of(unet).index)
     with pww_hip.miopen_find():
-        return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra_channels,
-                              on_step=on_step, negative_strength=negative_strength, **more)
+        if scheduler is base:
+            return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra_channels,
+                                  on_step=on_step, negative_strength=negative_strength, **more)
+        sampler.scheduler = scheduler      # for this call only
+        try:
+            return sampler.sample(conds, unconds, latents, timesteps, guidance_scale, weight_function, extra_channels=extra_channels,
+                                  on_step=on_step, negative_strength=negative_strength, **more)
+        finally:
+            sampler.scheduler = base
 
 
 def _finish(tools, latents, return_latents=False, decode=None):
@@ -531,6 +573,7 @@ def paint_with_words(
     controlnet_conditioning_scale=1.0,
     control_guidance_start: float = 0.0,
     control_guidance_end: float = 1.0,
+    sampler: Optional[str] = None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -590,7 +633,18 @@ def paint_with_words(
     layout pww_hip.controlnet.covers takes, in float16 / bfloat16 on the UNet's device. txt2img and img2img, every mode; it composes with
     negative regions, region prompts, LoRA adapters (which act on the UNet alone), long prompts and region strength. Scale 0, or an empty
     window, is the call without a ControlNet. ValueError: an image of another size, together with canvas_window. Not part of this: the
-    inpaint functions (a 9-channel UNet has no 4-channel ControlNet), the pipeline classes, pww_hip.dist."""
+    inpaint functions (a 9-channel UNet has no 4-channel ControlNet), the pipeline classes, pww_hip.dist.
+    `sampler` (extension; the reference's README lists "Support for other schedulers"): None (the default) samples with the scheduler in the
+    tools -- `preloaded_utils[4]`, or what `scheduler_type` loaded: the call of before. A name -- "euler", "euler_karras", "euler_a", "ddim",
+    "dpmpp_2m", "dpmpp_2m_karras" -- samples THIS call with that scheduler (sd_standin.schedulers: Euler, Euler ancestral, DDIM with eta 0,
+    DPM-Solver++(2M); `_karras`: Karras sigmas, rho 7), built with the betas and the prediction_type of the scheduler in the tools, which is
+    left as it is. These schedulers take every step as one native launch (pww_hip.steps; PWW_STEP=0: their own step()), and in hipGraph mode
+    the graph captured for one serves all. They compose with negative regions, region prompts, LoRA adapters, long prompts, ControlNets,
+    canvases, img2img and inpainting. region_strength with a name that builds a steps_offset = 1 scheduler ("ddim", "dpmpp_2m",
+    "dpmpp_2m_karras") stays refused (ValueError): pass a scheduler constructed with steps_offset=0 in `preloaded_utils` (or a
+    `scheduler_type` that builds one) instead -- that is accepted. Any other value: ValueError, before any model is touched. The pipeline
+    classes take the scheduler they are constructed with."""
+    check_sampler(sampler)
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     check_region_prompts(region_prompts, region_base_weight, region_feather, negative_color_context)
@@ -609,6 +663,8 @@ def paint_with_words(
         start, more["hold"] = partial(_held_images, init_images=[init_image]), hold
     if control is not None:   # (and so is a call without a ControlNet)
         more["control"] = control
+    if sampler is not None:   # (and so is a call without a sampler name)
+        more["sampler_name"] = sampler
     latents = _generate(tools, device, [color_context], [color_map_image], [input_prompt], [seed], num_inference_steps, guidance_scale,
                         weight_function, unconditional_input_prompt, start, strength, shared=True, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=[negative_color_context], negative_strength=negative_strength,
@@ -648,6 +704,7 @@ def paint_with_words_batch(
     controlnet_conditioning_scale=1.0,
     control_guidance_start: float = 0.0,
     control_guidance_end: float = 1.0,
+    sampler: Optional[str] = None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -668,7 +725,8 @@ def paint_with_words_batch(
     region_strength_feather: see paint_with_words; one dict for all requests or one (or None) per seed -- all requests run the same steps:
     from the step that releases the largest strength any of them names. controlnet / control_image / controlnet_conditioning_scale /
     control_guidance_start / control_guidance_end: see paint_with_words; control_image is one image for all requests or one per seed (with a
-    list of nets: a list with such an entry per net)."""
+    list of nets: a list with such an entry per net). sampler: see paint_with_words; one name for every request."""
+    check_sampler(sampler)
     check_prompt_chunks(max_prompt_chunks)
     check_negative_context(negative_color_context, negative_strength)
     seeds = list(seeds)
@@ -693,6 +751,8 @@ def paint_with_words_batch(
         start, more["hold"] = partial(_held_images, init_images=inits), hold
     if control is not None:   # (and so is a call without a ControlNet)
         more["control"] = control
+    if sampler is not None:   # (and so is a call without a sampler name)
+        more["sampler_name"] = sampler
     latents = _generate(tools, device, ctxs, maps, prompts, seeds, num_inference_steps, guidance_scale, weight_function,
                         unconditional_input_prompt, start, strength, shared=shared, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=negs, negative_strength=negative_strength, region_prompts=_region_requests(region_prompts, n),

@@ -14,7 +14,7 @@ from PIL import Image
 from pww_hip import ops
 from .paint_with_words import (LMSDiscreteScheduler, _tools, _generate, _finish, _broadcast, _batch_requests, check_prompt_chunks,
                                check_negative_context, check_region_prompts, check_loras, _region_requests, preprocess, _encode_scaled,
-                               _extract_seed_and_sigma_from_context)
+                               _extract_seed_and_sigma_from_context, check_sampler)
 
 
 def _as_uint8_pixels(image, channels):
@@ -165,6 +165,7 @@ def paint_with_words_inpaint(
     region_loras=None,
     controlnet=None,
     control_image=None,
+    sampler: Optional[str] = None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -172,7 +173,8 @@ def paint_with_words_inpaint(
 ):
     """reference :137-270. negative_color_context / negative_strength / region_prompts / region_base_weight / region_feather /
     max_prompt_chunks / lora / region_loras (extensions): see paint_with_words; controlnet / control_image are refused (ValueError). The region masks are read from the color map resized to the init image: its size
-    must be 8 x the latent's (a multiple of 32)."""
+    must be 8 x the latent's (a multiple of 32). sampler (extension): see paint_with_words."""
+    check_sampler(sampler)
     check_prompt_chunks(max_prompt_chunks)
     _no_controlnet(controlnet, control_image)
     check_negative_context(negative_color_context, negative_strength)
@@ -184,7 +186,7 @@ def paint_with_words_inpaint(
                         strength, map_sizes=[init_image.size], shared=True, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=[negative_color_context], negative_strength=negative_strength,
                         region_prompts=_region_requests(region_prompts, 1), region_base_weight=region_base_weight, region_feather=region_feather,
-                        loras=loras)
+                        loras=loras, **({} if sampler is None else {"sampler_name": sampler}))
     out = _finish(tools, latents, return_latents)
     return out if return_latents else out[0]
 
@@ -215,6 +217,7 @@ def paint_with_words_inpaint_batch(
     region_loras=None,
     controlnet=None,
     control_image=None,
+    sampler: Optional[str] = None,
     region_prompts=None,
     region_base_weight: float = 0.0,
     region_feather: float = 0.0,
@@ -223,7 +226,8 @@ def paint_with_words_inpaint_batch(
     """len(seeds) inpainting requests through one denoise loop (see paint_with_words_batch): each of the image-like
     arguments and the prompt is one shared value or a sequence with one entry per seed; all init images of a call must
     have the same size. Image i equals the single-request call on request i. negative_color_context / negative_strength /
-    region_prompts / region_base_weight / region_feather / max_prompt_chunks / lora / region_loras: see paint_with_words_batch."""
+    region_prompts / region_base_weight / region_feather / max_prompt_chunks / lora / region_loras / sampler: see paint_with_words_batch."""
+    check_sampler(sampler)
     check_prompt_chunks(max_prompt_chunks)
     _no_controlnet(controlnet, control_image)
     check_negative_context(negative_color_context, negative_strength)
@@ -245,7 +249,8 @@ def paint_with_words_inpaint_batch(
                         unconditional_input_prompt, partial(_inpaint_start, init_images=inits, mask_images=masks), strength,
                         map_sizes=[im.size for im in inits], shared=shared, max_prompt_chunks=max_prompt_chunks,
                         negative_color_contexts=negs, negative_strength=negative_strength, region_prompts=_region_requests(region_prompts, n),
-                        region_base_weight=region_base_weight, region_feather=region_feather, loras=loras)
+                        region_base_weight=region_base_weight, region_feather=region_feather, loras=loras,
+                        **({} if sampler is None else {"sampler_name": sampler}))
     for c in strip:
         _extract_seed_and_sigma_from_context(c)
     return _finish(tools, latents, return_latents)

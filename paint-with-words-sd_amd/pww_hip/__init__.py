@@ -6,6 +6,7 @@ from . import ops
 from . import blocks
 from . import lora
 from . import controlnet
+from . import steps
 from .attention import QKProxy, ScaledW, inj_forward, install, uninstall, PwWAttnProcessor, pww_attention
 from .attnmaps import record_attention_maps, AttentionMaps
 

@@ -52,6 +52,10 @@ TEXT_LIB_PATH = os.environ.get("PWW_HIP_TEXT_LIB", os.path.join(_HERE, "libpww_h
 #   control   the residuals of a ControlNet: its 1 x 1 zero convolutions, the conditioning scale and the add into the UNet's skip tensors and
 #             mid-block output as ONE grouped GEMM (include/pww_hip_control.h): ops.control_residuals. Its spec is in SIDE_EXTRA below.
 CONTROL_LIB_PATH = os.environ.get("PWW_HIP_CONTROL_LIB", os.path.join(_HERE, "libpww_hip_control.so"))
+#   step      one sampler step as ONE elementwise launch: the guidance combine, the scheduler's affine update (Euler, Euler ancestral, DDIM,
+#             DPM-Solver++ 2M: seven numbers per step), the history write and the next UNet input (include/pww_hip_step.h): ops.sched_step.
+#             Its spec is in SIDE_EXTRA below.
+STEP_LIB_PATH = os.environ.get("PWW_HIP_STEP_LIB", os.path.join(_HERE, "libpww_hip_step.so"))
 
 PWW_OK, PWW_EINVAL, PWW_ENOTSUP, PWW_EHIP = 0, -22, -95, -5
 MIN_VERSION = 127        # oldest libpww_hip ABI (pww_version(): major * 100 + minor) this package drives
@@ -161,6 +165,12 @@ TEXT_ACT_QUICK_GELU, TEXT_ACT_GELU = 0, 1
 CONTROL_EXPORTS = ("pww_control_version", "pww_control_last_error", "pww_control_fwd", "pww_control_plan")
 CONTROL_MIN_VERSION = 100
 CONTROL_MAX_PROBLEMS, CONTROL_TILE_M, CONTROL_TILE_N = 16, 128, 64      # PWW_CONTROL_* of the header
+
+
+# every symbol include/pww_hip_step.h declares for libpww_hip_step.so
+STEP_EXPORTS = ("pww_step_version", "pww_step_last_error", "pww_step_fwd")
+STEP_MIN_VERSION = 100
+STEP_SRC_F32, STEP_ROW = 2, 7      # PWW_STEP_* of the header
 
 
 class AttnDesc(ctypes.Structure):
@@ -512,6 +522,9 @@ SIDE_EXTRA = {
         "pww_vaeenc_tail_chunks": ([_P(VaeEncTailDesc)], _int),
         "pww_vaeenc_tail_stats": ([_vp, _vp, _P(VaeEncTailDesc), _vp, _sz, _vp], _int),
         "pww_vaeenc_tail_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(VaeEncTailDesc), _vp, _sz, _vp], _int)}),
+    # missing_ok: the stock route (ops.cfg_combine, scheduler.step, scale_model_input, cat and cast) computes the same thing
+    "step": dict(path="STEP_LIB_PATH", exports=STEP_EXPORTS, min_version=STEP_MIN_VERSION, missing_ok=True, needs="the fused sampler step needs it", sigs={
+        "pww_step_fwd": ([_vp, _vp, _vp, _vp, _f32, _vp, _vp, _P(_f32), _i64, _i32, _i32, _i32, _vp], _int)}),
     # missing_ok: the stock route (the zero convolutions as modules, a multiplication by the scale word, the adds) computes the same thing
     "control": dict(path="CONTROL_LIB_PATH", exports=CONTROL_EXPORTS, min_version=CONTROL_MIN_VERSION, missing_ok=True, needs="the grouped ControlNet residual launch needs it", sigs={
         "pww_control_fwd": ([_P(ControlProblem), _P(ControlDesc), _vp, _vp], _int),
@@ -635,6 +648,11 @@ def load_text():
 def load_control():
     lib = _side.get("control")
     return lib if lib is not None else load_side("control")
+
+
+def load_step():
+    lib = _side.get("step")
+    return lib if lib is not None else load_side("step")
 
 
 class experiments:

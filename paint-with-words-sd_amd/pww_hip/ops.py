@@ -1033,6 +1033,55 @@ def hold_apply(x, x0, z, S, theta, a, b):
     return x
 
 
+# ---- one sampler step as one launch (libpww_hip_step.so, include/pww_hip_step.h) -----------------------------------------------------------
+STEP_LAUNCHES = [0]      # launches of the step kernel (pww_hip.steps.stats)
+
+
+def sched_step(x, row, model, guidance_scale=0.0, h=None, z=None, u=None):
+    """One sampler step, IN PLACE on x (and returns it). x fp32 [n, C, h, w] contiguous; row the step's seven numbers (p, r, a, b, c, e, d':
+    pww_hip.steps.plan); model the model output -- a (cond, uncond) pair of float16 / bfloat16 tensors of x's shape, combined with
+    guidance_scale as uncond + g (cond - uncond), or ONE fp32 tensor of x's shape. h fp32 like x or None: the previous step's q, read if
+    c != 0 and overwritten with this step's. z fp32 like x or None: unit noise, read if e != 0. u None, or a float16 / bfloat16 tensor
+    [copies * n, C, h, w]: the next UNet input x' / d', every one of the `copies` row classes the same. Tensors are taken as they lie
+    (nothing is copied); the arithmetic and its order are the header's. One launch."""
+    pair = isinstance(model, (tuple, list))
+    m0, m1 = (model[0], model[1]) if pair else (model, None)
+    _require_gpu(x, h, z, u, m0, m1)
+    row = [float(v) for v in row]
+    if len(row) != _lib.STEP_ROW:
+        raise PwwHipError("sched_step needs a row of %d numbers (got %d)" % (_lib.STEP_ROW, len(row)))
+    if x.dtype != torch.float32 or any(t is not None and (t.dtype != torch.float32 or t.shape != x.shape) for t in (h, z)):
+        raise PwwHipError("sched_step needs float32 x, h and z of one shape")
+    if pair:
+        if m0.dtype not in _DT or m1.dtype != m0.dtype or m0.shape != x.shape or m1.shape != x.shape:
+            raise PwwHipError("sched_step: the cond / uncond pair must be two float16 / bfloat16 tensors of x's shape %s (got %s %s and %s %s)"
+                              % (tuple(x.shape), tuple(m0.shape), m0.dtype, tuple(m1.shape), m1.dtype))
+        src = _DT[m0.dtype]
+    else:
+        if m0.dtype != torch.float32 or m0.shape != x.shape:
+            raise PwwHipError("sched_step: a single model output must be float32 of x's shape %s (got %s %s)" % (tuple(x.shape), tuple(m0.shape), m0.dtype))
+        src = _lib.STEP_SRC_F32
+    copies, out = 0, 0
+    if u is not None:
+        if u.dtype not in _DT or u.dim() != x.dim() or u.shape[1:] != x.shape[1:] or u.shape[0] % x.shape[0]:
+            raise PwwHipError("sched_step: u must be float16 / bfloat16 [copies * n, ...] for x %s (got %s %s)" % (tuple(x.shape), tuple(u.shape), u.dtype))
+        copies, out = u.shape[0] // x.shape[0], _DT[u.dtype]
+    tensors = [t for t in (x, h, z, u, m0, m1) if t is not None]
+    if not all(t.is_contiguous() for t in tensors):
+        raise PwwHipError("sched_step needs contiguous tensors (x and h are written in place)")
+    if len({t.device for t in tensors}) != 1:
+        raise PwwHipError("sched_step needs its tensors on one device")
+    lib = _lib.load_step()
+    if lib is None:
+        raise PwwHipError("libpww_hip_step.so not found at %s: ops.sched_step needs it %s" % (_lib.STEP_LIB_PATH, _lib._HINT))
+    host = (ctypes.c_float * _lib.STEP_ROW)(*row)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.pww_step_fwd(_ptr(x), _ptr(h), _ptr(m0), _ptr(m1), float(guidance_scale), _ptr(z), _ptr(u), host, x.numel(), copies, src, out,
+                                    _stream()), "pww_step_fwd", lib)
+    STEP_LAUNCHES[0] += 1
+    return x
+
+
 # ---- GroupNorm (+ per-(image, channel) addend, + SiLU) of the blocks that call the attention path ------------------------------------
 def group_norm(x, num_groups, weight=None, bias=None, eps=1e-5, add=None, act=None, workspace=None, out=None, pre_bias=None):
     """act(GroupNorm(x + add[:, :, None, None])) for a [B, C, H, W] float16 / bfloat16 tensor in NCHW-contiguous or channels_last memory

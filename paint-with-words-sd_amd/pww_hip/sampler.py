@@ -31,6 +31,11 @@ ControlNet's encoder on the same rows, then one grouped launch per net that scal
 skip tensors. The hint (the embedded control image) lives in a static tensor, one row per UNet row; the conditioning scale in a device word
 that is rewritten before every evaluation: 0 outside the guidance window, where "eager" and "folded" skip the ControlNet and "graph" replays
 its ONE graph with the word at 0.
+Euler, Euler ancestral, DDIM and DPM-Solver++(2M) (pww_hip/steps.py: the schedulers `steps.covers` knows) take every step as ONE launch
+(ops.sched_step, outside the captured graph): the guidance combine, the scheduler's update as seven numbers, the history write and the next
+UNet input -- written straight into the graph's static input in "graph" -- where LMS and PLMS keep ops.cfg_combine + scheduler.step +
+scale_model_input + cat + cast, launch for launch. The plan is built once per request and the history tensor kept here; the scheduler
+object's state is not advanced. PWW_STEP=0 keeps scheduler.step everywhere.
 """
 import numpy as np
 import torch
@@ -39,6 +44,7 @@ from . import ops
 from . import attnmaps
 from . import lora as _lora
 from . import controlnet as _controlnet
+from . import steps as _steps
 from .attention import install, refresh_kv_cache, refresh_orig_cache, ROW_GATE, KV_CACHE, COEFF_SLOTS, CoeffSlots, COMPACT_W, COMPACT_IDX, GATED_ROWS, COND_ROWS, BIAS_COLS, ATTN_RECORDER
 from .conditioning import PwWContext
 
@@ -350,7 +356,8 @@ class _GraphedUNet:
             self.reset()
             self.static_in = torch.empty_like(x)
             self.static_t = torch.zeros((), dtype=torch.float32, device=x.device)
-        self.static_in.copy_(x)
+        if x is not self.static_in:      # (the fused step launch writes the next input into static_in itself)
+            self.static_in.copy_(x)
         self.static_t.fill_(float(t_value))
         slots = context.get(COEFF_SLOTS)
         key = "all" if slots is not None and not slots.unsupported else step
@@ -656,6 +663,17 @@ class PwWSampler:
         K = blend["K"] if blend is not None else 0
         calls = self._lora_calls        # eager mode with LoRA adapters loaded: every batch-1 call has its own one-row assignment
         plain_unet = unet
+        # the schedulers steps.covers knows: one launch per step (ops.sched_step) instead of cfg_combine + scheduler.step + the next step's
+        # scale_model_input + cat + cast. `fused`: the rows of the request, the history tensor where a row reads it, and u, the next UNet
+        # input -- not for canvas, region-strength and inpainting requests, which make their input as before
+        fused = None
+        if _steps.route(sch, latents):
+            rows = _steps.plan(sch, timesteps)
+            latents = latents.clone()      # the launch writes in place: the caller's tensor stays what it was, as with scheduler.step
+            fused = {"rows": rows, "draws": _steps.stochastic(sch), "u": None,
+                     "h": torch.empty(latents.shape, dtype=torch.float32, device=latents.device) if any(r[4] != 0.0 for r in rows) else None,
+                     "feeds": (canvas is None and hold is None and extra_channels is None and latents.is_contiguous()
+                               and udt in (torch.float16, torch.bfloat16))}      # (an fp32 UNet takes the launch without u, too)
         for i, t in enumerate(timesteps):
             sigma, _ = self._sigma_and_index(i, t)
             if control is not None:
@@ -668,7 +686,10 @@ class PwWSampler:
                 unet = control[1] if live else plain_unet
                 if not live and self.mode != "graph":
                     _controlnet._STATS["skipped_steps"] += 1
-            if canvas is None:
+            x2 = None
+            if fused is not None and fused["u"] is not None:
+                x = x2 = fused["u"]      # the last launch's u: scaled, rounded to the UNet's type, one replica per row class
+            elif canvas is None:
                 x = sch.scale_model_input(latents, t)
             else:
                 # the windows' rows, scaled and rounded to the UNet's type by one launch: [n_w, C, h, w] for the batch-1 calls of "eager",
@@ -702,7 +723,8 @@ class PwWSampler:
                 out = torch.cat([eps_c] + [torch.cat(r) for r in eps_r] + [eps_u]) if K or canvas is not None else None
             else:
                 folded.update({"SIGMA": sigma, "WEIGHT_FUNCTION": weight_function})
-                x2 = torch.cat([x] * (K + 2), dim=0).to(udt) if canvas is None else x
+                if x2 is None:
+                    x2 = torch.cat([x] * (K + 2), dim=0).to(udt) if canvas is None else x
                 if self.mode == "graph":
                     slots = folded[COEFF_SLOTS]
                     if not slots.unsupported and not slots.update(weight_function, sigma):
@@ -722,10 +744,14 @@ class PwWSampler:
                 combine = ops.region_combine if out.dtype in (torch.float16, torch.bfloat16) else region_blend_fp32
                 noise_pred = combine(out, blend["masks"], blend["weights"], blend["scales"], guidance_scale)
             elif eps_c.dtype in (torch.float16, torch.bfloat16):
-                noise_pred = ops.cfg_combine(eps_c, eps_u, guidance_scale)     # fp32, :501-503
+                # (the fused step launch combines the pair itself)
+                noise_pred = (eps_c, eps_u) if fused is not None else ops.cfg_combine(eps_c, eps_u, guidance_scale)     # fp32, :501-503
             else:
                 noise_pred = eps_u + guidance_scale * (eps_c - eps_u)
-            latents = sch.step(noise_pred, t, latents).prev_sample
+            if fused is None:
+                latents = sch.step(noise_pred, t, latents).prev_sample
+            else:
+                latents = self._fused_step(fused, i, len(timesteps), noise_pred, guidance_scale, latents, (K + 2) if self.mode != "eager" else 1, udt)
             if hold is not None:
                 # the pixels the next step does not release go back to the init latent at that step's noise level: one launch, in place, outside
                 # the captured graph in hipGraph mode
@@ -738,12 +764,38 @@ class PwWSampler:
                     # for bit. The launch reads and writes NCHW memory, so such a latent goes through an NCHW copy and back.)
                     latents.copy_(ops.hold_apply(latents.contiguous(), hold["init"], hold["noise"], hold["strength"], theta, a, b))
             if on_step is not None:
-                on_step(i, t, latents)
+                on_step(i, t, latents if fused is None else latents.clone())      # (the next launch overwrites the latent: a callback may keep what it is handed)
         # did any fused cross-attention launch of this request time out in its hand-off? One 4-byte device -> host copy behind an
         # event (ops.FusedErrorWatch): looked at when the next request starts and by check_errors() -- never a host stall here
         if self._scratch_modules is None:
             self._scratch_modules = [m for m in self.unet.modules() if m.__class__.__name__ in ("CrossAttention", "Attention")]
         self.handoff_pending = self._errors.post(self._scratch_modules)
+        return latents
+
+    def _fused_step(self, fused, i, T, model, guidance_scale, latents, copies, udt):
+        """Step i of T of a request on the fused route: ONE ops.sched_step, in place on the latent (outside the captured graph in hipGraph
+        mode, as the hold launch is). model: the (cond, uncond) pair of the UNet's type, or the fp32 blend of a region-prompt / canvas
+        request. A stochastic scheduler's noise is drawn here with the one torch.randn call its own step() makes, in the same place of the
+        loop, so both routes see the same noise under one seed. The next UNet input goes into fused["u"]: the graph's static input once it
+        exists, else a buffer of this request; not behind the last step, and not for requests that make their input as before."""
+        z = torch.randn(latents.shape, dtype=torch.float32, device=latents.device) if fused["draws"] else None
+        if isinstance(model, tuple):
+            model = tuple(m if m.is_contiguous() else m.contiguous() for m in model)
+        elif not model.is_contiguous():
+            model = model.contiguous()
+        u = None
+        if fused["feeds"] and i + 1 < T:
+            shape = (copies * latents.shape[0],) + tuple(latents.shape[1:])
+            static = self._graphed.static_in if self._graphed is not None else None
+            if static is not None and tuple(static.shape) == shape and static.dtype == udt and static.is_contiguous():
+                u = static
+            else:
+                u = fused["u"] if fused["u"] is not None and fused["u"] is not static else torch.empty(shape, dtype=udt, device=latents.device)
+        fused["u"] = u
+        if latents.is_contiguous():
+            return ops.sched_step(latents, fused["rows"][i], model, guidance_scale, h=fused["h"], z=z, u=u)
+        # (an img2img latent may carry channels_last strides and keeps them, as in the hold launch below: the step runs on an NCHW copy)
+        latents.copy_(ops.sched_step(latents.contiguous(), fused["rows"][i], model, guidance_scale, h=fused["h"], z=z))
         return latents
 
     def _lora_call(self, rows, context, n):
